@@ -14,7 +14,10 @@ so its host syncs never delay the next K1) runs on a side stream while steps i+1
 are hashed (keys triple-buffered); every step's hash AND grouping complete inside the
 timed region (--no-overlap serialises them).
 
-Output: ONE JSON line on rank 0 (driver contract), with
+Output: ONE JSON line on rank 0 (driver contract).  A plain run sets up, warms up, times
+--steps steps and prints the headline (value, ms_per_step, config; `headline`);
+--dump-outputs DIR also writes the last timed step's keys and representatives
+(`dump_outputs`).  Everything below is measured after the timed steps, only with --full:
   roofline      — K1 (sd_cas_sampled_kernel; K1G at N=1), timed by HIP events on its own
                   stream, priced as SURVEY.md §8(d) prices it: 953 compressions x 792 spec
                   int32 ops per file / kernel time vs the guide's int32 VALU peak (256 CUs x 4
@@ -109,9 +112,18 @@ def main() -> None:
     ap.add_argument("--unfused", action="store_true",
                     help="N=1: K1 + the standalone grouping chain on the side stream (the round-2 "
                          "pipeline) instead of K1G (K1 partitioning its own keys) + bucket tables")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else the line "
+                         "can carry (roofline, fused / group / exchange legs, sustained, e2e, "
+                         "cpu_baseline); a plain run times the steps and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's cas keys and Object representatives to "
+                         "DIR/<name>.npy (float64, see dump_outputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     rehearsal = bool(os.environ.get("SD_BENCH_ONE_DEVICE"))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N`: launch the N ranks ourselves, before any GPU call here
@@ -293,6 +305,21 @@ def main() -> None:
     k1_ms_ranks = km.cpu().tolist()
     kern_ms = max(k1_ms_ranks)
 
+    head = headline(args, world, F, dt, sharded, fused)
+    if args.dump_outputs:
+        # what a caller of the timed path holds after its last step, before any later leg
+        # reuses the buffers (res.rep resolves the exchange's overflow flag: collective)
+        step_rep = reps[(args.steps - 1) % NBUF] if fused else (res.rep if sharded else rep)
+        dump_outputs(args.dump_outputs, last_keys, step_rep, rank, world, args.seed)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if worker is not None:
+            worker.shutdown()
+        if sharded:
+            dist.destroy_process_group()
+        return
+
     # objects (for the record) — outside the timed region
     fused_rec = None
     if not sharded:
@@ -442,9 +469,7 @@ def main() -> None:
         e2e = e2e_leg(eng, content, sizes, last_keys, args, world, rank, dev,
                       dist if sharded else None)
 
-    files_total = world * F * args.steps
-    value = files_total / dt
-    gbs = files_total * MSG_BYTES / dt / 1e9
+    value = head["value"]
     achieved = F * MSG_BYTES / (kern_ms / 1e3) / 1e9  # per-GPU kernel GB/s
     valu = F * COMPRESSIONS * SPEC_OPS / (kern_ms / 1e3) / 1e12
     valu_hw = F * COMPRESSIONS * HW_OPS / (kern_ms / 1e3) / 1e12
@@ -475,38 +500,15 @@ def main() -> None:
     if world > 1:
         dist.barrier()
 
-    n_gpus = dist.get_world_size() if sharded else 1
     if rank == 0:
         line = {
-            "metric": "cas_ids/sec + hashed GB/s (whole node), 10M files at 1/2/4/8 MI355X",
-            "value": value,
-            "unit": "cas_ids/s",
-            "hashed_gb_per_s": gbs,
-            "n_gpus": n_gpus,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
+            **head,
             "vs_baseline": (value / cpu["value"]) if cpu else None,
             "vs_baseline_basis": ("value / cpu_baseline.value: BASELINE.json's north_star names the "
                                   "reference CPU path on the same box's host cores as THE baseline "
                                   "(BASELINE.md publishes no number for this metric)"),
-            "dtype": "u32",
-            "data": "synthetic (on-device splitmix64 content, 30% duplicates), resident in HBM",
             "config": {
-                "workload": "sampled-path cas_id (57,352-B BLAKE3 message/file) + Object grouping; "
-                            f"{F} files/GPU/step ({world * F} per step at n_gpus={world})",
-                "files_per_gpu": F,
-                "dup_permille": args.dup_permille,
-                "parallelism": f"shard-by-file x{world}" + (" + RCCL key-range all-to-all" if sharded else ""),
-                "pipeline": (("K1G (K1 + partition of its keys into fixed-capacity bucket "
-                              "regions) on the main stream; step i's bucket tables on a side "
-                              "stream overlap step i+1's K1G" if fused else
-                              "grouping of step i on a side stream (issued from a worker thread) "
-                              "overlaps hashing of steps i+1 and i+2") if args.overlap
-                             else "hash then group, serial"),
-                "grouping": "fused" if fused else ("exchange" if sharded else "standalone chain"),
+                **head["config"],
                 "objects": objects,
                 "exchange": None if not sharded else {
                     "backend": dist.get_backend(), "world_size": dist.get_world_size(),
@@ -591,6 +593,66 @@ def main() -> None:
         worker.shutdown()
     if sharded:
         dist.destroy_process_group()
+
+
+def headline(args, world: int, F: int, dt: float, sharded: bool, fused: bool) -> dict:
+    """The result line of a plain run (no --full): what the timed steps alone give."""
+    files_total = world * F * args.steps
+    return {
+        "metric": "cas_ids/sec + hashed GB/s (whole node), 10M files at 1/2/4/8 MI355X",
+        "value": files_total / dt,
+        "unit": "cas_ids/s",
+        "hashed_gb_per_s": files_total * MSG_BYTES / dt / 1e9,
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "dtype": "u32",
+        "data": "synthetic (on-device splitmix64 content, 30% duplicates), resident in HBM",
+        "config": {
+            "workload": "sampled-path cas_id (57,352-B BLAKE3 message/file) + Object grouping; "
+                        f"{F} files/GPU/step ({world * F} per step at n_gpus={world})",
+            "files_per_gpu": F,
+            "dup_permille": args.dup_permille,
+            "parallelism": f"shard-by-file x{world}" + (" + RCCL key-range all-to-all" if sharded else ""),
+            "pipeline": (("K1G (K1 + partition of its keys into fixed-capacity bucket "
+                          "regions) on the main stream; step i's bucket tables on a side "
+                          "stream overlap step i+1's K1G" if fused else
+                          "grouping of step i on a side stream (issued from a worker thread) "
+                          "overlaps hashing of steps i+1 and i+2") if args.overlap
+                         else "hash then group, serial"),
+            "grouping": "fused" if fused else ("exchange" if sharded else "standalone chain"),
+        },
+    }
+
+
+DUMP_BYTES_MAX = 60_000_000  # all ranks' .npy files together stay below 64 MB
+
+
+def dump_outputs(out_dir: str, keys, rep, rank: int, world: int, seed: int) -> None:
+    """--dump-outputs: the last timed step's results of this rank as float64 .npy files (every
+    value exact): `keys` [n, 2] = the high and low 32 bits of each file's u64 cas key, `rep`
+    [n] = the idx of the file owning each file's Object (local idx at N=1, global idx when
+    sharded).  n = the rank's files, or — when they would not fit the size bound — a sorted
+    sample of them drawn from `seed` alone, its file idx in `index` [n].  Rank r of an N > 1
+    run writes <name>_rank<r>.npy."""
+    import numpy as np
+    import torch
+    F = int(keys.numel())
+    n = min(F, DUMP_BYTES_MAX // world // 32)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    if n < F:
+        idx = np.sort(np.random.default_rng(seed).choice(F, n, replace=False))
+        sel = torch.from_numpy(idx).to(keys.device)
+        keys, rep = keys[sel], rep[sel]
+        np.save(os.path.join(out_dir, f"index{sfx}.npy"), idx.astype(np.float64))
+    k = keys.cpu().numpy().view(np.uint64)
+    np.save(os.path.join(out_dir, f"keys{sfx}.npy"),
+            np.stack([k >> np.uint64(32), k & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64))
+    np.save(os.path.join(out_dir, f"rep{sfx}.npy"), rep.cpu().numpy().astype(np.float64))
 
 
 def lsd_sort_leg(eng, keys, rep, objects, stream):

@@ -38,6 +38,58 @@ def test_gpus_zero_is_an_error():
     assert r.returncode != 0
 
 
+def test_steps_zero_is_an_error():
+    r = _run(["--steps", "0"])
+    assert r.returncode == 2 and "--steps" in r.stderr and r.stdout == ""
+
+
+def test_headline_of_a_plain_run():
+    """A plain run's line (no --full): the headline fields, from the timed steps alone."""
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+    args = types.SimpleNamespace(steps=4, warmup=1, dup_permille=300, overlap=True)
+    h = bench.headline(args, 1, 1000, 0.5, False, True)
+    assert h["ms_per_step"] == 125.0 and h["value"] == 8000.0 and h["steps"] == 4
+    assert h["unit"] == "cas_ids/s" and h["higher_is_better"] is True and h["dtype"] == "u32"
+    assert h["hashed_gb_per_s"] == 8000.0 * bench.MSG_BYTES / 1e9 and h["n_gpus"] == 1
+    assert h["config"]["grouping"] == "fused" and h["config"]["files_per_gpu"] == 1000
+    h = bench.headline(args, 2, 1000, 0.5, True, False)
+    assert h["value"] == 16000.0 and h["n_gpus"] == 2 and h["config"]["grouping"] == "exchange"
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float64 arrays that hold every u64 key and representative exactly; a
+    batch over the size bound is dumped as a sample that depends on the seed alone."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(5)
+    k = rng.integers(0, 2 ** 64, 1000, dtype=np.uint64)
+    k[:3] = [0, 2 ** 64 - 1, 2 ** 63]
+    keys = torch.from_numpy(k.view(np.int64))
+    rep = torch.arange(1000, dtype=torch.int32).flip(0)
+    bench.dump_outputs(str(tmp_path / "a"), keys, rep, 0, 1, 7)
+    assert sorted(os.listdir(tmp_path / "a")) == ["keys.npy", "rep.npy"]
+    dk, dr = np.load(tmp_path / "a" / "keys.npy"), np.load(tmp_path / "a" / "rep.npy")
+    assert dk.dtype == dr.dtype == np.float64 and dk.shape == (1000, 2) and dr.shape == (1000,)
+    assert ((dk[:, 0].astype(np.uint64) << np.uint64(32)) | dk[:, 1].astype(np.uint64) == k).all()
+    assert (dr == rep.numpy()).all()
+    # over the bound: rank 1 of 2 writes a sorted sample of 100 files, the same on every run
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 2 * 32 * 100)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), keys, rep.to(torch.int64), 1, 2, 7)
+    idx = np.load(tmp_path / "b" / "index_rank1.npy")
+    assert idx.shape == (100,) and (np.diff(idx) > 0).all() and idx.dtype == np.float64
+    assert (idx == np.load(tmp_path / "c" / "index_rank1.npy")).all()
+    i = idx.astype(np.int64)
+    dk, dr = np.load(tmp_path / "b" / "keys_rank1.npy"), np.load(tmp_path / "b" / "rep_rank1.npy")
+    assert ((dk[:, 0].astype(np.uint64) << np.uint64(32)) | dk[:, 1].astype(np.uint64) == k[i]).all()
+    assert (dr == rep.numpy()[i]).all()
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 2 * 32 * 100 + 3 * 128
+
+
 def test_visible_gpus_from_kfd_topology(tmp_path, monkeypatch):
     """spawn_ranks counts GPUs from the KFD topology (no HIP call in the parent): GPU nodes
     have a non-zero gfx_target_version, the CPU node 0; the *_VISIBLE_DEVICES lists narrow it."""

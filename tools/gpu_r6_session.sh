@@ -25,7 +25,7 @@
 #              10 s sustained each, 3 rounds (the HBM-energy lever)
 #   sortstall  SQ stall / instruction counters of the LSD grouping's kernels (two rocprofv3 --pmc passes)
 #   stresslong longer randomised stress on the final code (~15 min)
-#   repeat     the default `python bench.py` and the validator file path twice, on another box
+#   repeat     the default `python bench.py --full` and the validator file path twice, on another box
 #   valshapes  the validator file path on 20,000 small files, 150 files of 16-60 MiB, and 40 files
 #              of 128-192 MiB (streamed one by one)
 #   streamab   the streamed single-file path (40 files of 128-192 MiB; one 4 GiB file): in-tree vs
@@ -120,10 +120,10 @@ for step in "$@"; do
       SD_CAS_TRACE=1 SD_CONFIG1_PASSES=7 timeout -k 10 300 python3 -u tools/bench_configs.py --config 1 > $OUT/config1_trace.log 2>&1 || { echo CONFIG1_FAIL; exit 1; }
       grep -h '"config"' $OUT/config1_[12].log | cut -c1-600 ;;
     reh2)
-      SD_BENCH_ONE_DEVICE=1 SD_CPU_BASELINE_THREADS=16 timeout -k 10 500 python3 -u bench.py --gpus 2 --steps 10 --warmup 2 --files-per-gpu 262144 --e2e-files 1048576 > $OUT/bench_n2_rehearsal.log 2>&1 || { echo REH2_FAIL; tail -20 $OUT/bench_n2_rehearsal.log; exit 1; }
+      SD_BENCH_ONE_DEVICE=1 SD_CPU_BASELINE_THREADS=16 timeout -k 10 500 python3 -u bench.py --full --gpus 2 --steps 10 --warmup 2 --files-per-gpu 262144 --e2e-files 1048576 > $OUT/bench_n2_rehearsal.log 2>&1 || { echo REH2_FAIL; tail -20 $OUT/bench_n2_rehearsal.log; exit 1; }
       tail -1 $OUT/bench_n2_rehearsal.log | cut -c1-300 ;;
     reh4)
-      SD_BENCH_ONE_DEVICE=1 SD_CPU_BASELINE_THREADS=16 timeout -k 10 500 python3 -u bench.py --gpus 4 --steps 10 --warmup 2 --files-per-gpu 131072 --e2e-files 1048576 > $OUT/bench_n4_rehearsal.log 2>&1 || { echo REH4_FAIL; tail -20 $OUT/bench_n4_rehearsal.log; exit 1; }
+      SD_BENCH_ONE_DEVICE=1 SD_CPU_BASELINE_THREADS=16 timeout -k 10 500 python3 -u bench.py --full --gpus 4 --steps 10 --warmup 2 --files-per-gpu 131072 --e2e-files 1048576 > $OUT/bench_n4_rehearsal.log 2>&1 || { echo REH4_FAIL; tail -20 $OUT/bench_n4_rehearsal.log; exit 1; }
       tail -1 $OUT/bench_n4_rehearsal.log | cut -c1-300 ;;
     sorttests)
       timeout -k 10 600 python3 -u -m pytest tests/test_gpu_parity.py -m gpu -x -v -p no:cacheprovider --timeout 300 --timeout-method thread -k "sort or group or links or identifier" > $OUT/pytest_sort.log 2>&1 || { echo SORTTESTS_FAIL; tail -30 $OUT/pytest_sort.log; exit 1; }
@@ -168,7 +168,7 @@ for step in "$@"; do
       timeout -k 10 300 python3 -u tools/stress_paths.py --checksums --seconds 180 --seed 2031 > $OUT/stress_paths_long.log 2>&1 || { echo STRESS_FAIL; tail -5 $OUT/stress_paths_long.log; exit 1; }
       for f in stress_parity_long stress_fused_long stress_links_long stress_paths_long; do tail -1 $OUT/$f.log | cut -c1-200; done ;;
     repeat)
-      timeout -k 10 400 python3 -u bench.py > $OUT/bench_default.log 2>&1 || { echo BENCH_FAIL; tail -20 $OUT/bench_default.log; exit 1; }
+      timeout -k 10 400 python3 -u bench.py --full > $OUT/bench_default.log 2>&1 || { echo BENCH_FAIL; tail -20 $OUT/bench_default.log; exit 1; }
       tail -1 $OUT/bench_default.log | cut -c1-200
       for k in 1 2; do
         timeout -k 10 300 python3 -u tools/prof_checksums.py --no-device --paths 2000 --path-runs 6 > $OUT/validator_paths_$k.log 2>&1 || { echo VAL_FAIL; tail -20 $OUT/validator_paths_$k.log; exit 1; }

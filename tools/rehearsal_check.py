@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Checks a one-GPU rehearsal of the N-GPU bench line (SD_BENCH_ONE_DEVICE=1 bench.py --gpus N,
-VERDICT r5 #3): pulls the JSON line out of the log (gloo's connection chatter surrounds it) and
+"""Checks a one-GPU rehearsal of the N-GPU bench line (SD_BENCH_ONE_DEVICE=1 bench.py --full
+--gpus N): pulls the JSON line out of the log (gloo's connection chatter surrounds it) and
 checks what the driver's N-GPU run will need — n_gpus N, the G-specific exchange slot sizes,
 no timed step overflowed its fixed capacity, no host sync per step, and non-null roofline /
 group / cpu_baseline / e2e with e2e parity.  Prints one JSON summary (and writes the bare line
