@@ -34,8 +34,7 @@ namespace sdcas {
 // tail chunk.  A lane fetches one whole 128-B line (a block pair, 8 x dwordx4 issued back
 // to back) per batch, so each line is consumed while it is still in L2 (fetching 64 B per
 // block let the other half be evicted between blocks and doubled the HBM traffic), and
-// both lines of an iteration are in flight together (16 x dwordx4); the other waves of the
-// SIMD cover their latency.
+// each line is requested one compression ahead of its first block (cas_lane_sampled).
 
 constexpr uint32_t SAMPLED_PAIRS = SAMPLED_CONTENT_LEN / 128;  // 448
 constexpr uint32_t SAMPLED_CHUNKS = SAMPLED_CONTENT_LEN / 1024;  // 56 full chunks
@@ -69,6 +68,31 @@ __device__ __forceinline__ void compress_pair(uint32_t (&cv)[8], const uint4 (&A
   c1 = A[7].w;
 }
 
+// load_pair pinned where the source puts it: the machine scheduler otherwise sinks a line's
+// loads down the basic block towards the next line's (same base register), which takes the
+// lead that K1's schedule below is built for away again.
+__device__ __forceinline__ void load_pair_here(const uint4* __restrict__ q, uint32_t P,
+                                               uint4 (&buf)[8]) {
+  __builtin_amdgcn_sched_barrier(0);
+  load_pair(q, P, buf);
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// compress_pair's two blocks separately: the first block of line P (its 2-word carry c0, c1
+// is the tail of line P - 1), and the second.
+__device__ __forceinline__ void compress_lo(uint32_t (&cv)[8], const uint4 (&A)[8], uint32_t c0,
+                                            uint32_t c1, uint32_t ctr, uint32_t f) {
+  const uint32_t m[16] = {c0, c1, A[0].x, A[0].y, A[0].z, A[0].w, A[1].x, A[1].y,
+                          A[1].z, A[1].w, A[2].x, A[2].y, A[2].z, A[2].w, A[3].x, A[3].y};
+  compress(cv, m, ctr, 0u, BLOCK_LEN, f);
+}
+__device__ __forceinline__ void compress_hi(uint32_t (&cv)[8], const uint4 (&A)[8], uint32_t ctr,
+                                            uint32_t f) {
+  const uint32_t m[16] = {A[3].z, A[3].w, A[4].x, A[4].y, A[4].z, A[4].w, A[5].x, A[5].y,
+                          A[5].z, A[5].w, A[6].x, A[6].y, A[6].z, A[6].w, A[7].x, A[7].y};
+  compress(cv, m, ctr, 0u, BLOCK_LEN, f);
+}
+
 // The 5-deep chaining-value stack lives in LDS, word-major [depth][word][thread] so every
 // push/pop is a conflict-free dword access.  It is touched once per 1 KiB chunk (16
 // compressions), and moving its 40 words per lane out of VGPRs takes the kernel from 3
@@ -96,25 +120,10 @@ struct LdsStack {
 template <int BLK = SAMPLED_BLOCK>
 __device__ __forceinline__ uint64_t cas_lane_sampled(const uint4* __restrict__ q, uint64_t size,
                                                      LdsStack<BLK>& stk) {
-  uint32_t c0 = (uint32_t)size, c1 = (uint32_t)(size >> 32);
   uint4 A[8], B[8];
   uint32_t cv[8];
-  for (uint32_t c = 0; c < SAMPLED_CHUNKS; ++c) {
-    set_iv(cv);
-#pragma unroll 1
-    for (uint32_t pp = 0; pp < 4; ++pp) {  // 4 x (pair A, pair B) = 16 blocks
-      // both lines at the iteration start: a pair prefetched across the back edge was
-      // renamed and copied back (32 v_mov_b64 per iteration, 687.5 VALU instructions per
-      // compression); the load latency is covered by the SIMD's other three waves
-      // (681.5 per compression, +0.3-0.5 %: profiles/r05/ab_k1_prefetch/)
-      const uint32_t P = 8u * c + 2u * pp;
-      load_pair(q, P, A);
-      load_pair(q, P + 1, B);
-      compress_pair(cv, A, c0, c1, c, pp == 0 ? (uint32_t)CHUNK_START : 0u, 0u);
-      compress_pair(cv, B, c0, c1, c, 0u, pp == 3 ? (uint32_t)CHUNK_END : 0u);
-    }
-    // left-balanced tree: merge while the completed-chunk count has trailing zeros
-    uint32_t total = c + 1;
+  // left-balanced tree: merge while the completed-chunk count has trailing zeros
+  auto merge_push = [&](uint32_t total) {
     while ((total & 1u) == 0u) {
       uint32_t left[8];
       stk.pop(left);
@@ -122,7 +131,42 @@ __device__ __forceinline__ uint64_t cas_lane_sampled(const uint4* __restrict__ q
       total >>= 1;
     }
     stk.push(cv);
+  };
+  // The 448 lines are one flat sequence through two buffers, each refilled IN PLACE: A holds
+  // the even lines and B the odd ones, and a buffer's next line is requested one compression
+  // after its last block, once the first block of the OTHER buffer's line has read the
+  // 2-word carry from the buffer's tail where it lies.  So every line is requested one
+  // compression before its first block, nothing is renamed across the back edge and no
+  // carry is copied (679.0 VALU instructions per compression in this loop, 101 VGPRs).
+  // Requesting a line right after its buffer's last block gives it two compressions of
+  // lead, but the carry then has to be copied out of the buffer first (2 moves per line)
+  // and it measured slower than this (profiles/k1_pipeline/).
+  B[7].z = (uint32_t)size;  // the carry into line 0: the le64(size) prefix
+  B[7].w = (uint32_t)(size >> 32);
+  load_pair(q, 0, A);
+  for (uint32_t c = 0;; ++c) {
+    set_iv(cv);
+#pragma unroll 1
+    for (uint32_t pp = 0; pp < 4; ++pp) {  // 4 x (line in A, line in B) = 16 blocks
+      const uint32_t P = 8u * c + 2u * pp;
+      compress_lo(cv, A, B[7].z, B[7].w, c, pp == 0 ? (uint32_t)CHUNK_START : 0u);
+      load_pair_here(q, P + 1, B);  // P is even and < 448: so is P + 1
+      compress_hi(cv, A, c, 0u);
+      compress_lo(cv, B, A[7].z, A[7].w, c, 0u);
+      // Wave-uniform guard: no line >= 448 is ever requested (a batch's last row may end
+      // with its allocation).  It is the loop's EXIT and not a branch around the loads: a
+      // conditional load joins the old and the new buffer in a phi, which came out as a
+      // second buffer and 64 v_mov_b64 per iteration (152 VGPRs, 3 waves per SIMD).
+      if (P + 2u >= SAMPLED_PAIRS) goto last_block;
+      load_pair_here(q, P + 2, A);
+      compress_hi(cv, B, c, pp == 3 ? (uint32_t)CHUNK_END : 0u);
+    }
+    merge_push(c + 1);
   }
+last_block:  // line 447 is in B; nothing is left to request
+  compress_hi(cv, B, SAMPLED_CHUNKS - 1, CHUNK_END);
+  merge_push(SAMPLED_CHUNKS);
+  const uint32_t c0 = B[7].z, c1 = B[7].w;
   // tail chunk 56: the last 8 content bytes (the carry), one 8-byte block
   {
     const uint32_t m[16] = {c0, c1, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
