@@ -456,6 +456,40 @@ int sd_cas_checksums_dev(sd_cas_ctx* ctx, const void* d_arena, uint64_t arena_by
 int sd_cas_file_checksums(sd_cas_ctx* ctx, const char* const* paths, size_t n, char* out_hex,
                           int32_t* status);
 
+/* ---- cas_id + file_checksum from one copy of each file ----------------------------------
+ * Both columns of a file_path row — cas_id (cas.rs:23-62) and integrity_checksum
+ * (validation/hash.rs:11-25) — from WHOLE file contents, so a caller that holds (or reads)
+ * every byte for the checksum does not gather and read the file a second time for its cas_id.
+ *
+ * hash_contents: the cas keys of n whole contents resident in HBM, laid out as for
+ * sd_cas_checksums_dev — content i = d_arena + d_offs[i] (16-B aligned), d_lens[i] bytes
+ * (u64, <= 64 GiB) = the file's size, readable to the 16-B round-up of its end and for 16
+ * bytes from its start, ending within arena_bytes; n <= 2^24.  A content of up to 100 KiB is
+ * hashed whole by the packed kernels where it lies; a longer one is hashed by K1P straight
+ * from its header, four samples and footer (no gather row).  Length 0 hashes le64(0) like the
+ * packed path (the no-cas_id rule for empty files belongs to the path level).  The bounds are
+ * checked on the device first and the call waits for that verdict only: SD_CAS_EINVAL when a
+ * buffer breaks them — nothing is then read and d_keys is not written — otherwise the hashing
+ * is enqueued on the stream and the call returns. */
+int sd_cas_hash_contents_dev(sd_cas_ctx* ctx, const void* d_arena, uint64_t arena_bytes,
+                             const uint64_t* d_offs, const uint64_t* d_lens, size_t n,
+                             uint64_t* d_keys, void* stream);
+/* The same plus the validator's batch chain over the same buffers, with one bounds check:
+ * d_keys as above, d_digests[32 i .. 32 i + 32) as sd_cas_checksums_dev.  Blocking. */
+int sd_cas_identify_validate_dev(sd_cas_ctx* ctx, const void* d_arena, uint64_t arena_bytes,
+                                 const uint64_t* d_offs, const uint64_t* d_lens, size_t n,
+                                 uint64_t* d_keys, uint8_t* d_digests, void* stream);
+/* One read (and one stat) per path for both: out_keys / cas_status / out_sizes are exactly
+ * what sd_cas_file_metadata_from_paths returns for the path (SD_CAS_STATUS_NO_CAS for length
+ * 0, -EISDIR, -errno; key 0 then), out_hex / ck_status exactly what sd_cas_file_checksums
+ * returns.  A file hashed in the validator's windows gets its cas key there, from the bytes
+ * already in HBM; a file that leaves the windows (larger than half a window, irregular, or
+ * changed since the stat) gets its checksum as in sd_cas_file_checksums and its key from the
+ * path gather with the size of that one stat.  Blocking. */
+int sd_cas_identify_validate_paths(sd_cas_ctx* ctx, const char* const* paths, size_t n,
+                                   uint64_t* out_keys, int32_t* cas_status, uint64_t* out_sizes,
+                                   char* out_hex, int32_t* ck_status);
+
 /* ---- multi-device, single process -------------------------------------
  * One context per shard; shard i lives on devices[i] (a device may host several shards).
  * Grouping pulls each shard's key range from every other shard with peer copies over

@@ -170,6 +170,17 @@ extern "C" {
                                 stream: *mut c_void) -> c_int;
     pub fn sd_cas_file_checksums(ctx: *mut sd_cas_ctx, paths: *const *const c_char, n: usize,
                                  out_hex: *mut c_char, status: *mut i32) -> c_int;
+    pub fn sd_cas_hash_contents_dev(ctx: *mut sd_cas_ctx, d_arena: *const c_void, arena_bytes: u64,
+                                    d_offs: *const u64, d_lens: *const u64, n: usize,
+                                    d_keys: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_cas_identify_validate_dev(ctx: *mut sd_cas_ctx, d_arena: *const c_void, arena_bytes: u64,
+                                        d_offs: *const u64, d_lens: *const u64, n: usize,
+                                        d_keys: *mut u64, d_digests: *mut u8,
+                                        stream: *mut c_void) -> c_int;
+    pub fn sd_cas_identify_validate_paths(ctx: *mut sd_cas_ctx, paths: *const *const c_char, n: usize,
+                                          out_keys: *mut u64, cas_status: *mut i32,
+                                          out_sizes: *mut u64, out_hex: *mut c_char,
+                                          ck_status: *mut i32) -> c_int;
     pub fn sd_cas_multi_create(devices: *const c_int, ndev: c_int, out: *mut *mut sd_cas_multi) -> c_int;
     pub fn sd_cas_multi_destroy(m: *mut sd_cas_multi);
     pub fn sd_cas_multi_count(m: *const sd_cas_multi) -> c_int;
@@ -512,6 +523,64 @@ impl HipCas {
                 }
             })
             .collect())
+    }
+
+    /// Both columns of a file_path row from one read (and one stat) per file
+    /// (`sd_cas_identify_validate_paths`): per path the cas part of `FileMetadata::new` with the
+    /// metadata length it was decided from, as `file_metadata` returns them, and the
+    /// `file_checksum` result, as `file_checksums` returns it.
+    pub fn identify_validate(&mut self, paths: &[&Path])
+        -> io::Result<Vec<(Result<Option<CasId>, io::Error>, u64, io::Result<String>)>> {
+        let cs: Vec<CString> = paths
+            .iter()
+            .map(|p| CString::new(p.as_os_str().as_encoded_bytes()).expect("NUL in path"))
+            .collect();
+        let ptrs: Vec<*const c_char> = cs.iter().map(|c| c.as_ptr()).collect();
+        let n = paths.len();
+        let mut keys = vec![0u64; n];
+        let mut cas_status = vec![0i32; n];
+        let mut sizes = vec![0u64; n];
+        let mut out = vec![0 as c_char; 65 * n.max(1)];
+        let mut status = vec![0i32; n];
+        let rc = unsafe {
+            sd_cas_identify_validate_paths(self.ctx, ptrs.as_ptr(), n, keys.as_mut_ptr(),
+                                           cas_status.as_mut_ptr(), sizes.as_mut_ptr(),
+                                           out.as_mut_ptr(), status.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(self.err(rc));
+        }
+        Ok((0..n)
+            .map(|i| {
+                let cas = match cas_status[i] {
+                    0 => Ok(Some(CasId(keys[i]))),
+                    SD_CAS_STATUS_NO_CAS => Ok(None),
+                    e => Err(io::Error::from_raw_os_error(-e)),
+                };
+                let ck = if status[i] != 0 {
+                    Err(io::Error::from_raw_os_error(-status[i]))
+                } else {
+                    Ok(unsafe { CStr::from_ptr(out.as_ptr().add(65 * i)) }.to_string_lossy().into_owned())
+                };
+                (cas, sizes[i], ck)
+            })
+            .collect())
+    }
+
+    /// cas keys of whole file contents resident in device memory (`sd_cas_hash_contents_dev`).
+    ///
+    /// # Safety
+    /// `d_arena` must point to `arena_bytes` readable bytes, `d_offs` / `d_lens` / `d_keys` to `n`
+    /// u64 each, all in device memory of this context's GPU.
+    pub unsafe fn hash_contents_dev(&mut self, d_arena: *const c_void, arena_bytes: u64,
+                                    d_offs: *const u64, d_lens: *const u64, n: usize,
+                                    d_keys: *mut u64) -> io::Result<()> {
+        let rc = sd_cas_hash_contents_dev(self.ctx, d_arena, arena_bytes, d_offs, d_lens, n, d_keys,
+                                          ptr::null_mut());
+        if rc != 0 {
+            return Err(self.err(rc));
+        }
+        Ok(())
     }
 
     /// Canonical Object grouping of device-resident keys (see `sd_cas_group_dev`); returns

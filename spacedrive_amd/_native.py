@@ -78,6 +78,9 @@ SIGNATURES = [
     ("sd_cas_file_checksum", _i, [_vp, _cp, _cp, ctypes.POINTER(_i)]),
     ("sd_cas_checksums_dev", _i, [_vp, _vp, _u64, _vp, _vp, _sz, _vp, _vp]),
     ("sd_cas_file_checksums", _i, [_vp, _vp, _sz, _vp, _vp]),
+    ("sd_cas_hash_contents_dev", _i, [_vp, _vp, _u64, _vp, _vp, _sz, _vp, _vp]),
+    ("sd_cas_identify_validate_dev", _i, [_vp, _vp, _u64, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("sd_cas_identify_validate_paths", _i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     ("sd_cas_multi_create", _i, [_vp, _i, ctypes.POINTER(_vp)]),
     ("sd_cas_multi_destroy", None, [_vp]),
     ("sd_cas_multi_count", _i, [_vp]),

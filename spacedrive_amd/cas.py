@@ -312,6 +312,26 @@ class CasEngine:
             digests[i] = None
         return digests, -status
 
+    def identify_validate(self, paths: Sequence[str]):
+        """Both columns of a file_path row from one read (and one stat) per file
+        (sd_cas_identify_validate_paths): returns (keys, cas_status, sizes, digests, errnos) —
+        the first three exactly as file_metadata_from_paths, the last two as file_checksums."""
+        n = len(paths)
+        keep, parr = _path_array(paths)
+        keys = np.zeros(n, dtype=np.uint64)
+        cas_status = np.zeros(n, dtype=np.int32)
+        sizes = np.zeros(n, dtype=np.uint64)
+        out = ctypes.create_string_buffer(65 * max(n, 1))
+        status = np.zeros(n, dtype=np.int32)
+        if n:
+            self._check(self.L.sd_cas_identify_validate_paths(
+                self.h, parr, n, _np_ptr(keys), _np_ptr(cas_status), _np_ptr(sizes), out,
+                _np_ptr(status)), "identify_validate_paths")
+        digests = np.frombuffer(out, dtype="S65", count=n).astype("U64").tolist() if n else []
+        for i in np.flatnonzero(status).tolist():
+            digests[i] = None
+        return keys, cas_status, sizes, digests, -status
+
     # ---- device-resident (torch tensors as HBM buffers) ----------------------------------
     def hash_sampled(self, content, sizes, keys, stride: Optional[int] = None,
                      n: Optional[int] = None, stream: Optional[int] = None) -> None:
@@ -529,6 +549,28 @@ class CasEngine:
         ab = int(arena.numel() * arena.element_size()) if arena_bytes is None else int(arena_bytes)
         self._check(self.L.sd_cas_checksums_dev(self.h, _ptr(arena), ab, _ptr(offs), _ptr(lens), n,
                                                 _ptr(out), _stream(stream)), "checksums_dev")
+
+    def hash_contents(self, arena, offs, lens, keys, arena_bytes: Optional[int] = None,
+                      stream: Optional[int] = None) -> None:
+        """cas keys of whole file contents where they lie in HBM (sd_cas_hash_contents_dev):
+        content i = arena[offs[i] : offs[i] + lens[i]] as for checksums_dev, lens[i] = the
+        file's size; files over 100 KiB are hashed straight from their header, samples and
+        footer.  keys int64 [n].  Raises CasError (EINVAL) when a buffer breaks the bounds;
+        keys is then untouched."""
+        n = int(offs.numel())
+        ab = int(arena.numel() * arena.element_size()) if arena_bytes is None else int(arena_bytes)
+        self._check(self.L.sd_cas_hash_contents_dev(self.h, _ptr(arena), ab, _ptr(offs), _ptr(lens), n,
+                                                    _ptr(keys), _stream(stream)), "hash_contents")
+
+    def identify_validate_dev(self, arena, offs, lens, keys, digests,
+                              arena_bytes: Optional[int] = None, stream: Optional[int] = None) -> None:
+        """hash_contents + checksums_dev over the same buffers with one bounds check: keys
+        int64 [n], digests uint8 [n, 32]."""
+        n = int(offs.numel())
+        ab = int(arena.numel() * arena.element_size()) if arena_bytes is None else int(arena_bytes)
+        self._check(self.L.sd_cas_identify_validate_dev(self.h, _ptr(arena), ab, _ptr(offs), _ptr(lens),
+                                                        n, _ptr(keys), _ptr(digests), _stream(stream)),
+                    "identify_validate_dev")
 
     def synth_sampled(self, seed: int, file0: int, n: int, content, sizes, stride: int,
                       dup_permille: int = 0, stream: Optional[int] = None) -> None:

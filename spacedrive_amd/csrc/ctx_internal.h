@@ -161,6 +161,7 @@ struct sd_cas_ctx {
   DevBuf small;    // multi-device exchange buffers (sd_cas_multi_*)
   DevBuf cvbuf;    // file_checksum: one 32-B CV per 64 MiB segment
   DevBuf io;       // device copies of host arrays (sd_cas_identifier_links)
+  DevBuf inplace;  // cas_ids from whole contents: classify's lists (ordered across streams like ws)
   void* pinned = nullptr;
   size_t pinned_bytes = 0;
   uint64_t* d_scalar = nullptr;  // 8 x u64 scratch for counters
@@ -334,6 +335,12 @@ inline int sd_ensure(sd_cas_ctx* c, DevBuf& b, size_t bytes) {
 extern "C" hipError_t sd_dispatch_sampled(sd_cas_ctx* c, const uint8_t* content, uint64_t stride,
                                           const uint64_t* sizes, size_t n, uint64_t* keys,
                                           hipStream_t s);
+// K2 / K1L by batch size over ragged whole files (sd_hip_cas.cpp); sorts in c->ws, which the
+// caller has sized (sd_packed_workspace_bytes) and acquired
+extern "C" hipError_t sd_dispatch_packed(sd_cas_ctx* c, const uint8_t* arena, const uint64_t* offs,
+                                         const uint32_t* lens, const uint64_t* sizes, size_t n,
+                                         uint64_t* keys, hipStream_t s);
+extern "C" size_t sd_packed_workspace_bytes(const sd_cas_ctx* c, size_t n);
 
 inline int sd_ensure_pinned(sd_cas_ctx* c, size_t bytes) {
   if (bytes <= c->pinned_bytes) return SD_CAS_OK;

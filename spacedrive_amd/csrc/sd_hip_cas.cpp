@@ -45,12 +45,13 @@ uint32_t sd_dbg_violations_group_hash();
 uint32_t sd_dbg_violations_group();
 uint32_t sd_dbg_violations_checksum();
 uint32_t sd_dbg_violations_links();
+uint32_t sd_dbg_violations_inplace();
 }  // namespace sdcas
 // debug library only (libsd_hip_cas_debug.so, not in the ABI header): invariant violations
 // counted by the device checks of sd_debug.h since the library was loaded
 extern "C" uint64_t sd_cas_debug_violations(void) {
   return (uint64_t)sd_dbg_violations_group_hash() + sd_dbg_violations_group() +
-         sd_dbg_violations_checksum() + sd_dbg_violations_links();
+         sd_dbg_violations_checksum() + sd_dbg_violations_links() + sd_dbg_violations_inplace();
 }
 #endif
 
@@ -227,6 +228,7 @@ void sd_cas_ctx_destroy(sd_cas_ctx* c) {
   if (c->small.p) (void)hipFree(c->small.p);
   if (c->cvbuf.p) (void)hipFree(c->cvbuf.p);
   if (c->io.p) (void)hipFree(c->io.p);
+  if (c->inplace.p) (void)hipFree(c->inplace.p);
   if (c->d_scalar) (void)hipFree(c->d_scalar);
   if (c->gtotals) (void)hipFree(c->gtotals);
   if (c->gcursor) (void)hipFree(c->gcursor);
@@ -317,6 +319,34 @@ hipError_t sd_dispatch_sampled(sd_cas_ctx* c, const uint8_t* content, uint64_t s
                        sizes + full, r, keys + full, c->chunkpar_seg(r, true), s);
 }
 
+// Whole-file batch dispatch.  Small batches: K1L, a wave per file, no sort.  Otherwise K2,
+// or K1L with 4 files per wave: the files are visited by descending chunk count (one stable
+// radix pass) so the lanes of a wave (K2) / the files of a wave (K1L) match.
+// workspace (c->ws): length keys | sorted keys | order | sort workspace
+size_t sd_packed_workspace_bytes(const sd_cas_ctx* c, size_t n) {
+  if (n < c->latency_packed && c->chunkpar_seg(n, false) == 64) return 0;
+  return 2 * up256(n * 8) + up256(n * 4) + sort_workspace_bytes(n);
+}
+
+hipError_t sd_dispatch_packed(sd_cas_ctx* c, const uint8_t* arena, const uint64_t* offs,
+                              const uint32_t* lens, const uint64_t* sizes, size_t n, uint64_t* keys,
+                              hipStream_t s) {
+  const bool k1l = n < c->latency_packed;
+  if (k1l && c->chunkpar_seg(n, false) == 64)
+    return hash_chunkpar(arena, offs, 0, lens, 0, sizes, n, keys, 64, s);
+  const size_t kb = up256(n * 8), ob = up256(n * 4);
+  char* p = (char*)c->ws.p;
+  uint64_t* lkeys = (uint64_t*)p;
+  uint64_t* skeys = (uint64_t*)(p + kb);
+  uint32_t* order = (uint32_t*)(p + 2 * kb);
+  void* sws = p + 2 * kb + ob;
+  hipError_t e = length_keys(lens, n, lkeys, s);
+  if (e == hipSuccess) e = radix_sort_pairs(lkeys, nullptr, skeys, order, n, 0, length_key_bits(n), sws, s);
+  if (e != hipSuccess) return e;
+  if (k1l) return hash_chunkpar(arena, offs, 0, lens, 0, sizes, n, keys, 16, s, order);
+  return hash_packed(arena, offs, lens, sizes, order, n, keys, s);
+}
+
 int sd_cas_hash_sampled_dev(sd_cas_ctx* c, const void* d_content, uint64_t stride,
                             const uint64_t* d_sizes, size_t n, uint64_t* d_keys, void* stream) {
   if (!c) return SD_CAS_EINVAL;
@@ -339,31 +369,15 @@ int sd_cas_hash_packed_dev(sd_cas_ctx* c, const void* d_arena, const uint64_t* d
       n >= (1ull << 32))
     return fail(c, SD_CAS_EINVAL, "hash_packed: bad arguments");
   hipStream_t s = pick(c, stream);
-  const bool k1l = n < c->latency_packed;
-  if (k1l && c->chunkpar_seg(n, false) == 64) {  // small batch: a wave per file, no sort
-    HIP_TRY(c, hash_chunkpar((const uint8_t*)d_arena, d_offs, 0, d_lens, 0, d_sizes, n, d_keys,
-                             64, s));
+  const size_t wsb = sd_packed_workspace_bytes(c, n);
+  if (wsb == 0) {  // small batch: no sort, no workspace
+    HIP_TRY(c, sd_dispatch_packed(c, (const uint8_t*)d_arena, d_offs, d_lens, d_sizes, n, d_keys, s));
     return SD_CAS_OK;
   }
-  // K2, and K1L with 4 files per wave: visit the files by descending chunk count (one
-  // stable radix pass) so the lanes of a wave (K2) / the files of a wave (K1L) match.
-  // workspace: length keys | sorted keys | order | sort workspace
-  const size_t kb = up256(n * 8), ob = up256(n * 4);
-  int rc = ensure(c, c->ws, 2 * kb + ob + sort_workspace_bytes(n));
+  int rc = ensure(c, c->ws, wsb);
   if (rc) return rc;
-  char* p = (char*)c->ws.p;
-  uint64_t* lkeys = (uint64_t*)p;
-  uint64_t* skeys = (uint64_t*)(p + kb);
-  uint32_t* order = (uint32_t*)(p + 2 * kb);
-  void* sws = p + 2 * kb + ob;
   HIP_TRY(c, sd_ws_acquire(c, s));
-  HIP_TRY(c, length_keys(d_lens, n, lkeys, s));
-  HIP_TRY(c, radix_sort_pairs(lkeys, nullptr, skeys, order, n, 0, length_key_bits(n), sws, s));
-  if (k1l)
-    HIP_TRY(c, hash_chunkpar((const uint8_t*)d_arena, d_offs, 0, d_lens, 0, d_sizes, n, d_keys,
-                             16, s, order));
-  else
-    HIP_TRY(c, hash_packed((const uint8_t*)d_arena, d_offs, d_lens, d_sizes, order, n, d_keys, s));
+  HIP_TRY(c, sd_dispatch_packed(c, (const uint8_t*)d_arena, d_offs, d_lens, d_sizes, n, d_keys, s));
   HIP_TRY(c, sd_ws_release(c, s));
   return SD_CAS_OK;
 }

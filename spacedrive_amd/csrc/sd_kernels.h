@@ -50,4 +50,19 @@ hipError_t hash_chunkpar(const uint8_t* arena, const uint64_t* offs, uint64_t st
                          uint64_t n, uint64_t* keys, int seg, hipStream_t s,
                          const uint32_t* order = nullptr);
 int length_key_bits(uint64_t n);  // significant bits of the length_keys sort key
+// cas_ids from whole contents in place (cas_inplace.hip).  classify: the bounds verdict and
+// the routing of n contents (arena + offs[i], lens[i] bytes, u64) into ws
+// (inplace_workspace_bytes(n)): counters[0] = the checksum chain's bad flags (1: over 64 GiB,
+// 4: misaligned or past arena_bytes), counters[1] = sampled files, lens32[i] = lens[i] for a
+// whole file (<= 100 KiB) and 0 for a sampled or rejected one, sampled_idx = the sampled
+// files.  hash_inplace_sampled = K1P over such a list: keys[idx[k]] for k < n_idx.
+size_t inplace_workspace_bytes(uint64_t n);
+uint32_t* inplace_counters(void* ws);
+uint32_t* inplace_lens32(void* ws);
+uint32_t* inplace_sampled_idx(void* ws, uint64_t n);
+hipError_t inplace_classify(uint64_t arena_bytes, const uint64_t* offs, const uint64_t* lens,
+                            uint64_t n, void* ws, hipStream_t s);
+hipError_t hash_inplace_sampled(const uint8_t* arena, const uint64_t* offs, const uint64_t* lens,
+                                const uint32_t* idx, uint64_t n_idx, uint64_t* keys,
+                                hipStream_t s);
 }  // namespace sdcas

@@ -518,6 +518,86 @@ int sd_cas_checksums_dev(sd_cas_ctx* c, const void* d_arena, uint64_t arena_byte
   return SD_CAS_OK;
 }
 
+// ---- cas_ids from whole contents in place (cas_inplace.hip) -----------------------------
+
+// After inplace_classify on s: whole files through the packed dispatcher over classify's u32
+// lengths (sampled files count as empty there; their keys are rewritten next), then K1P over
+// the sampled list.  c->inplace and c->ws are sized and ws is acquired by the caller.
+static hipError_t contents_hash_classified(sd_cas_ctx* c, const uint8_t* arena, const uint64_t* offs,
+                                           const uint64_t* lens, size_t n, size_t n_sampled,
+                                           uint64_t* keys, hipStream_t s) {
+  void* iw = c->inplace.p;
+  hipError_t e = hipSuccess;
+  if (n_sampled < n) e = sd_dispatch_packed(c, arena, offs, inplace_lens32(iw), lens, n, keys, s);
+  if (e == hipSuccess)
+    e = hash_inplace_sampled(arena, offs, lens, inplace_sampled_idx(iw, n), n_sampled, keys, s);
+  return e;
+}
+
+// Both device entry points: classify, the bounds verdict (one read-back; a batch that breaks
+// the bounds is not read and writes nothing), then the cas hash and, with d_digests, the
+// checksum batch chain over the same buffers.
+static int contents_dev(sd_cas_ctx* c, const char* what, const void* d_arena, uint64_t arena_bytes,
+                        const uint64_t* d_offs, const uint64_t* d_lens, size_t n, uint64_t* d_keys,
+                        uint8_t* d_digests, bool digests, void* stream) {
+  if (!c) return SD_CAS_EINVAL;
+  if (n == 0) return SD_CAS_OK;
+  if (!d_arena || !d_offs || !d_lens || !d_keys || (digests && !d_digests) ||
+      ((uintptr_t)d_arena & 15) || ((uintptr_t)d_keys & 7) || ((uintptr_t)d_digests & 3) ||
+      n > (1u << 24))
+    return fail(c, SD_CAS_EINVAL, "%s: bad arguments", what);
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  int rc = ensure(c, c->inplace, inplace_workspace_bytes(n));
+  if (rc) return rc;
+  rc = ensure(c, c->ws, std::max(sd_packed_workspace_bytes(c, n),
+                                 digests ? checksum_batch_workspace_bytes(n, arena_bytes) : (size_t)0));
+  if (rc) return rc;
+  uint32_t verdict[2] = {0, 0};  // bad flags, sampled files
+  HIP_TRY(c, sd_ws_acquire(c, s));
+  HIP_TRY(c, inplace_classify(arena_bytes, d_offs, d_lens, n, c->inplace.p, s));
+  HIP_TRY(c, hipMemcpyAsync(verdict, inplace_counters(c->inplace.p), 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  if (verdict[0]) {
+    (void)sd_ws_release(c, s);
+    return fail(c, SD_CAS_EINVAL, "%s: %s", what,
+                (verdict[0] & 1) ? "a buffer is longer than 64 GiB"
+                                 : "a buffer is misaligned or extends past arena_bytes");
+  }
+  HIP_TRY(c, contents_hash_classified(c, (const uint8_t*)d_arena, d_offs, d_lens, n, verdict[1],
+                                      d_keys, s));
+  if (!digests) {
+    HIP_TRY(c, sd_ws_release(c, s));
+    return SD_CAS_OK;
+  }
+  // the chain's own flag can only still report its CV list's bound (overlapping buffers)
+  uint32_t* d_bad = (uint32_t*)(c->d_scalar + 6);
+  uint32_t bad = 0;
+  HIP_TRY(c, hipMemsetAsync(d_bad, 0, 4, s));
+  HIP_TRY(c, checksum_batch_device((const uint8_t*)d_arena, arena_bytes, d_offs, d_lens, n,
+                                   (uint32_t*)d_digests, d_bad, c->ws.p, s));
+  HIP_TRY(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, sd_ws_release(c, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  if (bad)
+    return fail(c, SD_CAS_EINVAL, "%s: the buffers' subtrees exceed arena_bytes' bound (overlapping buffers?)", what);
+  return SD_CAS_OK;
+}
+
+int sd_cas_hash_contents_dev(sd_cas_ctx* c, const void* d_arena, uint64_t arena_bytes,
+                             const uint64_t* d_offs, const uint64_t* d_lens, size_t n,
+                             uint64_t* d_keys, void* stream) {
+  return contents_dev(c, "hash_contents", d_arena, arena_bytes, d_offs, d_lens, n, d_keys, nullptr,
+                      false, stream);
+}
+
+int sd_cas_identify_validate_dev(sd_cas_ctx* c, const void* d_arena, uint64_t arena_bytes,
+                                 const uint64_t* d_offs, const uint64_t* d_lens, size_t n,
+                                 uint64_t* d_keys, uint8_t* d_digests, void* stream) {
+  return contents_dev(c, "identify_validate", d_arena, arena_bytes, d_offs, d_lens, n, d_keys,
+                      d_digests, true, stream);
+}
+
 // file_checksum over many paths.  The batch files are laid out in windows of up to CK_WIN
 // bytes / CK_WIN_FILES files in index order (one slot of up128(st_size + 1) per file: the
 // spare byte shows EOF, so a file that grew since stat fills its slot and is redone by the
@@ -533,11 +613,18 @@ int sd_cas_checksums_dev(sd_cas_ctx* c, const void* d_arena, uint64_t arena_byte
 // sit on the GPU's NUMA node (sd_cas_ctx_create).  Warm 2,000-file tmpfs set: 53.5-54.7 GB/s
 // vs 51.6-52.4 with one copy stream and 49.9-53.0 with the pump on the calling thread
 // (profiles/r06/validator/s7_*).  Pinned and device slot layout: offs | lens | digests | data.
-int sd_cas_file_checksums(sd_cas_ctx* c, const char* const* paths, size_t n, char* out_hex,
-                          int32_t* status) {
-  if (!c) return SD_CAS_EINVAL;
-  if (n == 0) return SD_CAS_OK;
-  if (!paths || !out_hex || !status) return fail(c, SD_CAS_EINVAL, "file_checksums: null argument");
+//
+// With out_keys (sd_cas_identify_validate_paths) the same read also gives each row's cas part
+// of FileMetadata::new, exactly as sd_cas_file_metadata_from_paths decides it: the stat pass
+// fills out_sizes and cas_status (-errno, -EISDIR, NO_CAS for length 0), and where a window
+// launches K3b it launches the contents hash (cas_inplace.hip) on the same offs / lens, thread
+// and stream; the slot header then holds 8 more bytes per file, the keys, which come back with
+// the digests.  A window member decided as hashed takes both results from the window; every
+// other row that still wants a key gets it from the path gather at the end, with the stat
+// pass's sizes (one stat per path decides the row).  out_keys == NULL: nothing of this runs.
+static int file_checksums_impl(sd_cas_ctx* c, const char* const* paths, size_t n, char* out_hex,
+                               int32_t* status, uint64_t* out_keys, int32_t* cas_status,
+                               uint64_t* out_sizes) {
   HIP_TRY(c, hipSetDevice(c->device));
   constexpr uint64_t CK_WIN = 128ull << 20;  // data bytes per window
   constexpr uint64_t CK_BIG = CK_WIN / 2;    // larger files stream on their own (64 MiB segments)
@@ -545,20 +632,32 @@ int sd_cas_file_checksums(sd_cas_ctx* c, const char* const* paths, size_t n, cha
   constexpr uint64_t CK_PIECE = (uint64_t)SD_CK_PIECE_KB << 10;  // read unit (a file's last piece takes the rest)
   constexpr uint64_t CK_COPY = (uint64_t)SD_CK_COPY_MB << 20;     // H2D unit of a window's landed prefix
   constexpr int CK_SLOTS = 3;
-  constexpr size_t HDR = CK_WIN_FILES * (8 + 8 + 32);
-  constexpr size_t SLOT = HDR + CK_WIN + 256;
+  const size_t HDR = CK_WIN_FILES * (8 + 8 + 32 + (out_keys ? 8 : 0));
+  const size_t SLOT = HDR + CK_WIN + 256;
   enum : uint8_t { K_BATCH = 0, K_STREAM = 1, K_ERROR = 2 };
   SdTrace tr(c->trace, "file_checksums", n);
   std::vector<uint64_t> fsize(n, 0);
   std::vector<uint8_t> kind(n, K_BATCH), big(n, 0);  // big: a regular file over CK_BIG
   for (size_t i = 0; i < n; i++) { status[i] = 0; out_hex[65 * i] = 0; }
+  std::vector<uint8_t> khave(out_keys ? n : 0, 0);  // the row's key comes from its window
+  if (out_keys)
+    for (size_t i = 0; i < n; i++) { out_keys[i] = 0; cas_status[i] = 0; out_sizes[i] = 0; }
   {  // stat pass
     std::atomic<size_t> next{0};
     c->pool.run(std::max(1u, std::min(16u, (unsigned)((n + 63) / 64))), [&]() {
       for (size_t i; (i = next.fetch_add(1)) < n;) {
         struct stat st;
-        if (stat(paths[i], &st) != 0) { status[i] = -errno; kind[i] = K_ERROR; continue; }
+        if (stat(paths[i], &st) != 0) {
+          status[i] = -errno;
+          kind[i] = K_ERROR;
+          if (out_keys) cas_status[i] = -errno;
+          continue;
+        }
         fsize[i] = (uint64_t)st.st_size;
+        if (out_keys) {  // FileMetadata::new's decision (file_identifier/mod.rs:63-86)
+          if (S_ISDIR(st.st_mode)) cas_status[i] = -EISDIR;
+          else if ((out_sizes[i] = fsize[i]) == 0) cas_status[i] = SD_CAS_STATUS_NO_CAS;
+        }
         // not a regular file (FIFO, device, ...): hash.rs's sequential reads, streamed
         if (fsize[i] > CK_BIG || !S_ISREG(st.st_mode)) kind[i] = K_STREAM;
         big[i] = fsize[i] > CK_BIG && S_ISREG(st.st_mode);
@@ -605,7 +704,12 @@ int sd_cas_file_checksums(sd_cas_ctx* c, const char* const* paths, size_t n, cha
   if (nw) {
     if ((rc = ensure_pinned(c, CK_SLOTS * SLOT))) return rc;
     if ((rc = ensure(c, c->staging, CK_SLOTS * SLOT))) return rc;
-    if ((rc = ensure(c, c->ws, checksum_batch_workspace_bytes(CK_WIN_FILES, CK_WIN)))) return rc;
+    size_t wsb = checksum_batch_workspace_bytes(CK_WIN_FILES, CK_WIN);
+    if (out_keys) {
+      for (size_t w = 0; w < nw; w++) wsb = std::max(wsb, sd_packed_workspace_bytes(c, wmem[w + 1] - wmem[w]));
+      if ((rc = ensure(c, c->inplace, inplace_workspace_bytes(CK_WIN_FILES)))) return rc;
+    }
+    if ((rc = ensure(c, c->ws, wsb))) return rc;
   }
   hipStream_t s = c->stream, cs = c->copy;
   hipEvent_t done[CK_SLOTS] = {}, landed = nullptr;
@@ -684,6 +788,15 @@ int sd_cas_file_checksums(sd_cas_ctx* c, const char* const* paths, size_t n, cha
       for (int j = 0; j < 32; j++) { o[2 * j] = hx[d[j] >> 4]; o[2 * j + 1] = hx[d[j] & 15]; }
       o[64] = 0;
     }
+    if (!out_keys) return;
+    // the window's keys follow its digests; a member whose key is not the window's (khave),
+    // or that has no cas_id, keeps key 0
+    const size_t m = wmem[w + 1] - wmem[w];
+    const uint8_t* kp = dg + 32 * m;
+    for (size_t k = wmem[w]; k < wmem[w + 1]; k++) {
+      const size_t i = mfile[k];
+      if (khave[i] && cas_status[i] == 0) memcpy(&out_keys[i], kp + 8 * (k - wmem[w]), 8);
+    }
   };
   uint32_t* d_bad = (uint32_t*)(c->d_scalar + 6);
   size_t ncopies = 0;
@@ -733,6 +846,7 @@ int sd_cas_file_checksums(sd_cas_ctx* c, const char* const* paths, size_t n, cha
           uint64_t* h_offs = (uint64_t*)pin;
           uint64_t* h_lens = h_offs + CK_WIN_FILES;
           const size_t m = wmem[wc + 1] - wmem[wc];
+          size_t sampled = 0;  // members the contents hash will route to K1P
           for (size_t k = wmem[wc]; k < wmem[wc + 1]; k++) {
             const size_t i = mfile[k], j = k - wmem[wc];
             h_offs[j] = moff[k];
@@ -744,6 +858,10 @@ int sd_cas_file_checksums(sd_cas_ctx* c, const char* const* paths, size_t n, cha
             // such a file exactly as hash.rs:15-21 does (1 MiB reads, stop at the first short one)
             if (got == mcap[k] || mirr[k].load() || got < fsize[i]) { kind[i] = K_STREAM; continue; }
             h_lens[j] = got;
+            sampled += got > MINIMUM_FILE_SIZE;
+            // the window's key is le64(got) || what was read: the row's key only when that is
+            // the metadata length too (a procfs file reads past its st_size of 0)
+            if (out_keys && got == fsize[i]) khave[i] = 1;
           }
           hipError_t e = hipSuccess;
           if (SD_CK_COPY_STREAMS > 1) {  // the header copy (on cs) after copy2's pieces too
@@ -757,8 +875,17 @@ int sd_cas_file_checksums(sd_cas_ctx* c, const char* const* paths, size_t n, cha
             e = checksum_batch_device((const uint8_t*)(dev + HDR), wbytes[wc], (const uint64_t*)dev,
                                       (const uint64_t*)dev + CK_WIN_FILES, m,
                                       (uint32_t*)(dev + CK_WIN_FILES * 16), d_bad, c->ws.p, s);
+          if (e == hipSuccess && out_keys) {  // the same buffers' cas keys, after the digests
+            e = inplace_classify(wbytes[wc], (const uint64_t*)dev, (const uint64_t*)dev + CK_WIN_FILES, m,
+                                 c->inplace.p, s);
+            if (e == hipSuccess)
+              e = contents_hash_classified(c, (const uint8_t*)(dev + HDR), (const uint64_t*)dev,
+                                           (const uint64_t*)dev + CK_WIN_FILES, m, sampled,
+                                           (uint64_t*)(dev + CK_WIN_FILES * 16 + m * 32), s);
+          }
           if (e == hipSuccess)
-            e = hipMemcpyAsync(pin + CK_WIN_FILES * 16, dev + CK_WIN_FILES * 16, m * 32, hipMemcpyDeviceToHost, s);
+            e = hipMemcpyAsync(pin + CK_WIN_FILES * 16, dev + CK_WIN_FILES * 16, m * (out_keys ? 40 : 32),
+                               hipMemcpyDeviceToHost, s);
           if (e == hipSuccess) e = hipEventRecord(done[b], s);
           if (e != hipSuccess) { hipfail(e, "window"); break; }
           ++issued;
@@ -853,7 +980,42 @@ int sd_cas_file_checksums(sd_cas_ctx* c, const char* const* paths, size_t n, cha
   tr.mark("streamed");
   for (size_t i = 0; i < n; i++)
     if (status[i]) out_hex[65 * i] = 0;
+  if (out_keys) {
+    // rows that want a key and did not get it from a window (big, irregular or changed
+    // files): the path gather, decided by the sizes of the stat pass above
+    std::vector<size_t> ri;
+    std::vector<const char*> rp;
+    std::vector<uint64_t> rs;
+    for (size_t i = 0; i < n; i++)
+      if (cas_status[i] == 0 && !khave[i]) { ri.push_back(i); rp.push_back(paths[i]); rs.push_back(out_sizes[i]); }
+    if (!ri.empty()) {
+      std::vector<uint64_t> rk(ri.size());
+      std::vector<int32_t> rst(ri.size());
+      if ((rc = sd_cas_generate_cas_ids_from_paths(c, rp.data(), rs.data(), ri.size(), rk.data(), rst.data())))
+        return rc;
+      for (size_t k = 0; k < ri.size(); k++) { out_keys[ri[k]] = rk[k]; cas_status[ri[k]] = rst[k]; }
+    }
+    tr.mark("gathered");
+  }
   return SD_CAS_OK;
+}
+
+int sd_cas_file_checksums(sd_cas_ctx* c, const char* const* paths, size_t n, char* out_hex,
+                          int32_t* status) {
+  if (!c) return SD_CAS_EINVAL;
+  if (n == 0) return SD_CAS_OK;
+  if (!paths || !out_hex || !status) return fail(c, SD_CAS_EINVAL, "file_checksums: null argument");
+  return file_checksums_impl(c, paths, n, out_hex, status, nullptr, nullptr, nullptr);
+}
+
+int sd_cas_identify_validate_paths(sd_cas_ctx* c, const char* const* paths, size_t n,
+                                   uint64_t* out_keys, int32_t* cas_status, uint64_t* out_sizes,
+                                   char* out_hex, int32_t* ck_status) {
+  if (!c) return SD_CAS_EINVAL;
+  if (n == 0) return SD_CAS_OK;
+  if (!paths || !out_keys || !cas_status || !out_sizes || !out_hex || !ck_status || n >= (1ull << 32))
+    return fail(c, SD_CAS_EINVAL, "identify_validate_paths: null argument");
+  return file_checksums_impl(c, paths, n, out_hex, ck_status, out_keys, cas_status, out_sizes);
 }
 
 }  // extern "C"
