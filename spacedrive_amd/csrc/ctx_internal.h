@@ -298,6 +298,12 @@ inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 // packed whole-file contents start on 128-B lines: a K2 lane's line pair is one cache line
 inline size_t up128(size_t x) { return (x + 127) & ~(size_t)127; }
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+// a 32-byte digest as 64 lower-case hex digits and a NUL
+inline void sd_hex32(const uint8_t d[32], char out[65]) {
+  static const char* hx = "0123456789abcdef";
+  for (int i = 0; i < 32; i++) { out[2 * i] = hx[d[i] >> 4]; out[2 * i + 1] = hx[d[i] & 15]; }
+  out[64] = 0;
+}
 
 // Grow a device buffer (on the CURRENT device).  Growing synchronises the device: call
 // outside hot loops / graph capture.

@@ -16,7 +16,6 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -30,29 +29,13 @@ using namespace sdcas;
 
 #include "sd_debug.h"
 #include "ctx_internal.h"
+#include "sd_piece_queue.h"
 
 // short local names for the shared helpers
 #define fail sd_fail
 #define pick sd_pick
 #define ensure sd_ensure
 #define ensure_pinned sd_ensure_pinned
-
-// A/B knobs of the file paths below (tools/build_variant.sh + tools/patch_define.py)
-#ifndef SD_CK_PIECE_KB
-#define SD_CK_PIECE_KB 1024
-#endif
-#ifndef SD_CK_COPY_MB
-#define SD_CK_COPY_MB 8
-#endif
-#ifndef SD_CK_PUMP_READS  // the pump thread also reads pieces when it has nothing to issue
-#define SD_CK_PUMP_READS 1
-#endif
-#ifndef SD_CK_PUMP_ON_POOL  // the pump on a pool thread (1) or on the calling thread (0)
-#define SD_CK_PUMP_ON_POOL 1
-#endif
-#ifndef SD_CK_COPY_STREAMS  // copies alternate over this many streams (1 or 2)
-#define SD_CK_COPY_STREAMS 2
-#endif
 
 
 extern "C" {
@@ -93,19 +76,65 @@ int sd_cas_checksum_dev(sd_cas_ctx* c, const void* d_data, uint64_t len, uint8_t
 // read on anything that returns short reads before its end (procfs seq_files give about one
 // page per read, FIFOs and FUSE/network mounts whatever is ready).
 // Two read modes, one result:
-//   * pieces (regular files; round 6, file_checksum_pieces): the file is planned from st_size
-//     as 64 MiB segments (a segment = one complete 65,536-chunk subtree) rotating over three
-//     pinned + device slots; 1 MiB pieces from one queue are read by the pool (bound to the
-//     GPU's NUMA node) while a pump on a pool thread copies every landed prefix to HBM over
-//     two copy streams and hashes each complete segment (K3) into its subtree CV — the
-//     validator job's piece queue (sd_cas_file_checksums) for one file.  A regular file whose
-//     reads show it is not read like a local file — a short pread before the planned end,
-//     data in the probe byte past st_size (it grew), an end before st_size — is redone
-//     sequentially;
-//   * sequential (everything else, and those redos): hash.rs's loop literally, 1 MiB read()s
-//     from the start, stopping after the first short one, through two pinned segment buffers.
+//   * pieces (regular files, file_checksums_pieces): the file is planned from st_size and read
+//     through the piece queue; a file whose reads show it is not read like a local file is
+//     redone sequentially;
+//   * sequential (everything else, and those redos, file_checksum_seq): hash.rs's loop literally.
 // The segment CVs are merged on the GPU (pair-and-promote, ROOT on the last parent); a file
 // of one segment is hashed with ROOT inside the segment.
+
+// The three slot events and the copies' event of the file paths, created and destroyed here only.
+struct SlotEvents {
+  hipEvent_t done[3] = {}, landed = nullptr;
+  bool ok = true;
+  SlotEvents() {
+    for (hipEvent_t* e : {&done[0], &done[1], &done[2], &landed})
+      ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+  }
+  ~SlotEvents() {
+    for (hipEvent_t e : {done[0], done[1], done[2], landed})
+      if (e) (void)hipEventDestroy(e);
+  }
+  SlotEvents(const SlotEvents&) = delete;
+};
+
+// The piece queue's device (sd_piece_queue.h): pinned slot -> staging slot over c->copy /
+// c->copy2, the work on c->stream.  begin() runs on the pump thread (HIP's current device is
+// per thread) and takes the workspace; zero: a flag word the unit kernels report into.
+struct QueueDev {
+  sd_cas_ctx* c;
+  uint32_t* zero;
+  SlotEvents ev;
+  int begin() {
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = sd_ws_acquire(c, c->stream);
+    if (e == hipSuccess && zero) e = hipMemsetAsync(zero, 0, 4, c->stream);
+    return e;
+  }
+  int copy(int k, size_t at, size_t bytes) {
+    return hipMemcpyAsync((char*)c->staging.p + at, (char*)c->pinned + at, bytes, hipMemcpyHostToDevice,
+                          k ? c->copy2 : c->copy);
+  }
+  int join(hipStream_t from, hipStream_t to) {
+    const hipError_t e = hipEventRecord(ev.landed, from);
+    return e == hipSuccess ? hipStreamWaitEvent(to, ev.landed, 0) : e;
+  }
+  int join_copies() { return join(c->copy2, c->copy); }
+  int join_compute() { return join(c->copy, c->stream); }
+  int record_done(int b) { return hipEventRecord(ev.done[b], c->stream); }
+  int query_done(int b, bool& ready) {
+    const hipError_t q = hipEventQuery(ev.done[b]);
+    ready = q == hipSuccess;
+    return q == hipErrorNotReady ? 0 : q;
+  }
+  void drain() {
+    for (hipStream_t x : {c->copy, c->copy2, c->stream}) (void)hipStreamSynchronize(x);
+  }
+};
+static int queue_failed(sd_cas_ctx* c, const char* call, const sdq::Result& r) {
+  return fail(c, SD_CAS_EHIP, "%s %s: %s", call, r.what, hipGetErrorString((hipError_t)r.err));
+}
+
 static int cv_capacity(sd_cas_ctx* c, DevBuf& cvb, size_t need_cvs, hipStream_t s) {
   if (need_cvs * 32 <= cvb.bytes) return SD_CAS_OK;
   DevBuf nb;
@@ -124,33 +153,26 @@ static int cv_capacity(sd_cas_ctx* c, DevBuf& cvb, size_t need_cvs, hipStream_t 
   return SD_CAS_OK;
 }
 
-// The pieces mode of file_checksum (see above), over one or many files in ONE queue: every
-// file is planned from its st_size (+ one probe byte) as 64 MiB segments; the segments of all
-// files, in file order, rotate over three pinned + device slots, and their 1 MiB pieces are
-// read by the pool while the pump copies landed prefixes (two copy streams), hashes each
-// complete segment (K3 at its chunk offset, ROOT inside for a one-segment file) and, after a
-// file's last segment, reduces its CVs into its digest — so a validator job's large files
-// stream back to back with no per-file fill and drain.  Each piece opens its file by path on
-// the pool thread that reads it (the pool's threads have private descriptor tables,
-// HostPool::set_private_fds: a descriptor opened on the calling thread is not theirs).  Per
-// file: digests[32 j], errs[j] = the errno of a failed open/read (0 otherwise), go_seq[j] = 1
-// when its reads were irregular (a short pread before its planned end, data in the probe byte,
-// an end before st_size): redo with hash.rs's sequential reads.  Returns SD_CAS_OK or a HIP /
-// allocation error.
+// The pieces mode of file_checksum, over one or many files in ONE queue: every file is planned
+// from its st_size (+ one probe byte: data there means the file grew) as 64 MiB segments (a
+// segment = one complete 65,536-chunk subtree); the segments of all files, in file order, are
+// the queue's units, so a validator job's large files stream back to back with no per-file
+// fill and drain.  A complete segment is hashed (K3 at its chunk offset, ROOT inside for a
+// one-segment file) and, after a file's last segment, the file's CVs are reduced into its
+// digest.  Per file: digests[32 j], errs[j] = the errno of a failed open/read (0 otherwise),
+// go_seq[j] = 1 when its reads were irregular (sdq::read_piece, or a segment that did not hold
+// exactly its planned bytes): redo with hash.rs's sequential reads.  Returns SD_CAS_OK or a
+// HIP / allocation error.
 static int file_checksums_pieces(sd_cas_ctx* c, const char* const* paths, const uint64_t* sizes,
                                  size_t nf, uint8_t* digests, int* errs, uint8_t* go_seq) {
   constexpr uint64_t SEG = 64ull << 20;  // 65,536 chunks: a complete left subtree
-  constexpr uint64_t PIECE = (uint64_t)SD_CK_PIECE_KB << 10;
-  constexpr uint64_t COPY = (uint64_t)SD_CK_COPY_MB << 20;
-  constexpr int SLOTS = 3;
   if (nf == 0) return SD_CAS_OK;
   struct Seg { uint32_t file; uint64_t k, len, want; };  // len: planned bytes, want: bytes to hash
-  struct Piece { uint32_t seg; uint64_t off, len; };     // off: from the segment's start
   std::vector<Seg> segs;
   std::vector<uint64_t> nreal(nf), cvbase(nf + 1, 0);
   uint64_t maxtotal = 0, maxreal = 1;
   for (size_t j = 0; j < nf; j++) {
-    const uint64_t total = sizes[j] + 1;  // + the probe byte: data there means the file grew
+    const uint64_t total = sizes[j] + 1;  // + the probe byte
     const uint64_t nplan = (total + SEG - 1) / SEG;
     nreal[j] = std::max<uint64_t>(1, (sizes[j] + SEG - 1) / SEG);  // segments holding data
     cvbase[j + 1] = cvbase[j] + nreal[j];
@@ -162,180 +184,70 @@ static int file_checksums_pieces(sd_cas_ctx* c, const char* const* paths, const 
     errs[j] = 0;
     go_seq[j] = 0;
   }
-  std::vector<Piece> pieces;
-  std::vector<size_t> spiece{0};
-  for (size_t g = 0; g < segs.size(); g++) {
-    const uint64_t np = std::max<uint64_t>(1, segs[g].len / PIECE);
-    for (uint64_t q = 0; q < np; q++)
-      pieces.push_back({(uint32_t)g, q * PIECE, q + 1 < np ? PIECE : segs[g].len - q * PIECE});
-    spiece.push_back(pieces.size());
-  }
-  const size_t ns = segs.size(), np = pieces.size();
   const uint64_t cap = std::min<uint64_t>(SEG, ((maxtotal + 4095) / 4096) * 4096);
-  const size_t sb = up256(cap + 16);
+  sdq::Plan pl;
+  pl.slot_bytes = up256(cap + 16);
+  for (const Seg& sg : segs) {
+    sdq::cut_pieces(sg.len, sdq::PIECE, [&](uint64_t off, uint64_t len) { pl.add_piece(off, len); });
+    pl.end_unit(sg.want);
+  }
   const uint64_t ncv = cvbase[nf];
-  hipStream_t s = c->stream, cs = c->copy;
+  hipStream_t s = c->stream;
   int rc = SD_CAS_OK;
-  if ((rc = ensure_pinned(c, SLOTS * sb)) || (rc = ensure(c, c->staging, SLOTS * sb))) return rc;
+  if ((rc = ensure_pinned(c, pl.slots * pl.slot_bytes)) || (rc = ensure(c, c->staging, pl.slots * pl.slot_bytes)))
+    return rc;
   if ((rc = ensure(c, c->ws, std::max({checksum_workspace_bytes(cap), checksum_workspace_bytes(1 << 20),
                                         2 * up256((maxreal + 255) / 256 * 32) + 512}))))
     return rc;
   if ((rc = cv_capacity(c, c->cvbuf, ncv + nf, s))) return rc;  // CVs, then the digests
   uint32_t* d_cv = (uint32_t*)c->cvbuf.p;
   uint32_t* d_dig = d_cv + 8 * ncv;
-  hipEvent_t done[SLOTS] = {}, landed = nullptr;
-  auto destroy_events = [&]() {
-    for (int b = 0; b < SLOTS; b++)
-      if (done[b]) (void)hipEventDestroy(done[b]);
-    if (landed) (void)hipEventDestroy(landed);
-  };
-  for (int b = 0; b < SLOTS; b++)
-    if (hipEventCreateWithFlags(&done[b], hipEventDisableTiming) != hipSuccess) {
-      destroy_events();
-      return fail(c, SD_CAS_EHIP, "file_checksum: event create");
-    }
-  if (hipEventCreateWithFlags(&landed, hipEventDisableTiming) != hipSuccess) {
-    destroy_events();
-    return fail(c, SD_CAS_EHIP, "file_checksum: event create");
-  }
-  std::unique_ptr<std::atomic<uint8_t>[]> fin(new std::atomic<uint8_t>[np]);
-  std::unique_ptr<std::atomic<uint64_t>[]> sgot(new std::atomic<uint64_t>[ns]);
-  std::unique_ptr<std::atomic<int>[]> ferr(new std::atomic<int>[nf]);
-  std::unique_ptr<std::atomic<uint8_t>[]> firr(new std::atomic<uint8_t>[nf]);
-  for (size_t p = 0; p < np; p++) fin[p].store(0, std::memory_order_relaxed);
-  for (size_t g = 0; g < ns; g++) sgot[g].store(0);
-  for (size_t j = 0; j < nf; j++) { ferr[j].store(0); firr[j].store(0); }
-  std::atomic<bool> abort{false};
-  std::atomic<size_t> next{0}, freed{0};
-  auto slot_free = [&](uint32_t g) { return g < freed.load(std::memory_order_acquire) + SLOTS; };
-  auto read_piece = [&](size_t p) {
-    const Piece& pc = pieces[p];
-    const Seg& sg = segs[pc.seg];
-    const uint32_t j = sg.file;
-    if (ferr[j].load(std::memory_order_relaxed) || firr[j].load(std::memory_order_relaxed)) return;
-    char* dst = (char*)c->pinned + (size_t)(pc.seg % SLOTS) * sb + pc.off;
-    const uint64_t foff = sg.k * SEG + pc.off;
-    const int fd = open(paths[j], O_RDONLY | O_CLOEXEC);
-    if (fd < 0) { ferr[j].store(errno); return; }
-    uint64_t got = 0;
-    bool was_short = false;
-    while (got < pc.len) {
-      ssize_t r = pread(fd, dst + got, pc.len - got, (off_t)(foff + got));
-      if (r < 0 && errno == EINTR) continue;
-      if (r < 0) { ferr[j].store(errno); break; }
-      if (r == 0) break;  // EOF
-      if (was_short) firr[j].store(1);  // data after a short read
-      if ((uint64_t)r < pc.len - got) was_short = true;
-      got += (uint64_t)r;
-    }
-    close(fd);
-    if (got < pc.len && foff + pc.len < sizes[j] + 1) firr[j].store(1);  // ended before the planned end
-    sgot[pc.seg].fetch_add(got);
-  };
-  auto worker = [&]() {
-    for (size_t p; !abort.load(std::memory_order_relaxed) && (p = next.fetch_add(1)) < np;) {
-      while (!slot_free(pieces[p].seg) && !abort.load(std::memory_order_relaxed)) std::this_thread::yield();
-      if (abort.load(std::memory_order_relaxed)) break;
-      read_piece(p);
-      fin[p].store(1, std::memory_order_release);
-    }
-  };
+  QueueDev dev{c, nullptr};
+  if (!dev.ev.ok) return fail(c, SD_CAS_EHIP, "file_checksum: event create");
+  // per segment: bytes read; per file: read error, irregular read (all zero-initialised)
+  std::vector<std::atomic<uint64_t>> sgot(segs.size());
+  std::vector<std::atomic<int>> ferr(nf);
+  std::vector<std::atomic<uint8_t>> firr(nf);
   std::vector<uint8_t> fok(nf, 1);  // (pump only) every segment of the file so far as planned
-  // the pump: copies landed prefixes, hashes complete segments and finished files, frees slots
-  auto pump = [&]() {
-    size_t kc = 0, issued = 0, retired = 0, ready = 0, ncopies = 0;
-    uint64_t sent = 0;
-    auto hipfail = [&](hipError_t e, const char* what) {
-      rc = fail(c, SD_CAS_EHIP, "file_checksum %s: %s", what, hipGetErrorString(e));
-      abort.store(true);
-    };
-    if (hipError_t e = hipSetDevice(c->device); e != hipSuccess) { hipfail(e, "setup"); return; }
-    if (hipError_t e = sd_ws_acquire(c, s); e != hipSuccess) { hipfail(e, "setup"); return; }
-    while (retired < ns && rc == SD_CAS_OK) {
-      if (retired < issued) {
-        const hipError_t q = hipEventQuery(done[retired % SLOTS]);
-        if (q == hipSuccess) {
-          freed.store(++retired, std::memory_order_release);
-          continue;
-        }
-        if (q != hipErrorNotReady) { hipfail(q, "segment sync"); break; }
-      }
-      bool progress = false;
-      if (kc < ns) {
-        const Seg& sg = segs[kc];
-        const size_t b = kc % SLOTS;
-        char* pin = (char*)c->pinned + b * sb;
-        char* dev = (char*)c->staging.p + b * sb;
-        while (ready < spiece[kc + 1] && fin[ready].load(std::memory_order_acquire)) ++ready;
-        const bool complete = ready == spiece[kc + 1];
-        const uint64_t hi = complete ? sg.want : std::min(sg.want, pieces[ready].off);
-        if (hi > sent && (hi - sent >= COPY || complete)) {
-          hipStream_t xs = (SD_CK_COPY_STREAMS > 1 && (ncopies & 1)) ? c->copy2 : cs;
-          const uint64_t hi16 = complete ? up16(hi) : hi;  // (K3 reads to the 16-B round-up)
-          const hipError_t e = hipMemcpyAsync(dev + sent, pin + sent, hi16 - sent, hipMemcpyHostToDevice, xs);
-          if (e != hipSuccess) { hipfail(e, "copy"); break; }
-          sent = hi16;
-          ++ncopies;
-          progress = true;
-        }
-        if (complete && sent >= sg.want) {
-          const uint32_t j = sg.file;
-          const bool last = sg.k + 1 == (sizes[j] + SEG) / SEG;  // (sizes[j] + 1 + SEG - 1) / SEG segments
-          // the segment must hold exactly its planned bytes (the probe byte none)
-          if (ferr[j].load() || firr[j].load() || sgot[kc].load() != (last ? sg.len - 1 : sg.len)) fok[j] = 0;
-          hipError_t e = hipSuccess;
-          if (fok[j] && sg.k < nreal[j]) {
-            if (SD_CK_COPY_STREAMS > 1) {
-              e = hipEventRecord(landed, c->copy2);
-              if (e == hipSuccess) e = hipStreamWaitEvent(s, landed, 0);
-            }
-            if (e == hipSuccess) e = hipEventRecord(landed, cs);
-            if (e == hipSuccess) e = hipStreamWaitEvent(s, landed, 0);
-            if (e == hipSuccess)
-              e = checksum_device((const uint8_t*)dev, sg.want, (sg.k * SEG) >> 10, nreal[j] == 1,
-                                  d_cv + 8 * (cvbase[j] + sg.k), c->ws.p, s);
-          }
-          if (e == hipSuccess && fok[j] && last)  // the file's digest
-            e = nreal[j] == 1 ? hipMemcpyAsync(d_dig + 8 * j, d_cv + 8 * cvbase[j], 32, hipMemcpyDeviceToDevice, s)
-                              : reduce_cvs_device(d_cv + 8 * cvbase[j], nreal[j], d_dig + 8 * j, c->ws.p, s);
-          if (e == hipSuccess) e = hipEventRecord(done[b], s);
-          if (e != hipSuccess) { hipfail(e, "segment"); break; }
-          ++issued;
-          ++kc;
-          sent = 0;
-          continue;
-        }
-      }
-      if (progress) continue;
-      size_t p = next.load(std::memory_order_relaxed);
-      if (SD_CK_PUMP_READS && p < np && slot_free(pieces[p].seg) && next.compare_exchange_strong(p, p + 1)) {
-        read_piece(p);
-        fin[p].store(1, std::memory_order_release);
-      } else {
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#else
-        std::this_thread::yield();
-#endif
-      }
-    }
+  auto read = [&](size_t p, size_t at) {
+    const uint32_t g = pl.punit[p], j = segs[g].file;
+    if (ferr[j].load(std::memory_order_relaxed) || firr[j].load(std::memory_order_relaxed)) return;
+    const uint64_t foff = segs[g].k * SEG + pl.poff[p];
+    const sdq::ReadResult r =
+        sdq::read_piece(paths[j], (char*)c->pinned + at, foff, pl.plen[p], foff + pl.plen[p] < sizes[j] + 1);
+    if (r.err) ferr[j].store(r.err);
+    if (r.irregular) firr[j].store(1);
+    sgot[g].fetch_add(r.got);
   };
-  std::atomic<bool> pump_taken{false};
-  const std::function<void()> pool_fn = [&]() {
-    if (!pump_taken.exchange(true)) pump(); else worker();
+  auto last_of_file = [&](const Seg& sg) { return sg.k + 1 == (sizes[sg.file] + SEG) / SEG; };
+  auto landed = [&](size_t g) {  // the segment must hold exactly its planned bytes (the probe byte none)
+    const Seg& sg = segs[g];
+    const uint32_t j = sg.file;
+    if (ferr[j].load() || firr[j].load() || sgot[g].load() != (last_of_file(sg) ? sg.len - 1 : sg.len)) fok[j] = 0;
+    return 0;
   };
-  c->pool.run2(std::max(2u, std::min(16u, (unsigned)std::min<size_t>(np + 1, 16))), pool_fn, []() {});
+  auto issue = [&](size_t g) {
+    const Seg& sg = segs[g];
+    const uint32_t j = sg.file;
+    hipError_t e = hipSuccess;
+    if (!fok[j]) return e;
+    if (sg.k < nreal[j])
+      e = checksum_device((const uint8_t*)c->staging.p + (g % pl.slots) * pl.slot_bytes, sg.want,
+                          (sg.k * SEG) >> 10, nreal[j] == 1, d_cv + 8 * (cvbase[j] + sg.k), c->ws.p, s);
+    if (e == hipSuccess && last_of_file(sg))  // the file's digest
+      e = nreal[j] == 1 ? hipMemcpyAsync(d_dig + 8 * j, d_cv + 8 * cvbase[j], 32, hipMemcpyDeviceToDevice, s)
+                        : reduce_cvs_device(d_cv + 8 * cvbase[j], nreal[j], d_dig + 8 * j, c->ws.p, s);
+    return e;
+  };
+  pl.threads = std::max(2u, std::min(16u, (unsigned)std::min<size_t>(pl.pieces() + 1, 16)));
+  const sdq::Result res = sdq::run(pl, c->pool, dev, read, landed, issue, [](size_t) {});
+  if (res.err) rc = queue_failed(c, "file_checksum segment", res);
   if (rc == SD_CAS_OK) {
     hipError_t e = hipMemcpyAsync(digests, d_dig, nf * 32, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) rc = fail(c, SD_CAS_EHIP, "checksum digests: %s", hipGetErrorString(e));
   }
   (void)sd_ws_release(c, s);
-  // nothing in flight may still read the pinned slots or write the CVs
-  (void)hipStreamSynchronize(cs);
-  (void)hipStreamSynchronize(c->copy2);
-  (void)hipStreamSynchronize(s);
-  destroy_events();
   for (size_t j = 0; j < nf; j++) {
     errs[j] = ferr[j].load();
     go_seq[j] = !errs[j] && !fok[j];
@@ -371,12 +283,9 @@ static int file_checksum_seq(sd_cas_ctx* c, int fd, const char* path, uint8_t di
   int rc = SD_CAS_OK;
   if ((rc = ensure_pinned(c, 2 * sb)) || (rc = ensure(c, c->staging, 2 * sb))) return rc;
   if ((rc = ensure(c, c->ws, checksum_workspace_bytes(SEG)))) return rc;
-  hipEvent_t done[2] = {nullptr, nullptr};
-  for (int i = 0; i < 2; i++)
-    if (hipEventCreateWithFlags(&done[i], hipEventDisableTiming) != hipSuccess) {
-      for (int k = 0; k < i; k++) (void)hipEventDestroy(done[k]);
-      return fail(c, SD_CAS_EHIP, "file_checksum: event create");
-    }
+  SlotEvents ev;  // (two of its slots)
+  if (!ev.ok) return fail(c, SD_CAS_EHIP, "file_checksum: event create");
+  hipEvent_t* done = ev.done;
   char* pin[2] = {(char*)c->pinned, (char*)c->pinned + sb};
   char* dev[2] = {(char*)c->staging.p, (char*)c->staging.p + sb};
   bool stopped = false;  // the first short read has happened
@@ -410,11 +319,8 @@ static int file_checksum_seq(sd_cas_ctx* c, int fd, const char* path, uint8_t di
     if (err_no) *err_no = (int)-neg;
     return fail(c, SD_CAS_EIO, "read(%s): %s", path, strerror((int)-neg));
   };
-  if (hipError_t e = sd_ws_acquire(c, s); e != hipSuccess) {
-    (void)hipEventDestroy(done[0]);
-    (void)hipEventDestroy(done[1]);
+  if (hipError_t e = sd_ws_acquire(c, s); e != hipSuccess)
     return fail(c, SD_CAS_EHIP, "file_checksum: %s", hipGetErrorString(e));
-  }
   uint64_t nseg = 1;
   const int64_t len0 = read_seg(pin[0]);
   if (len0 < 0) {
@@ -448,8 +354,6 @@ static int file_checksum_seq(sd_cas_ctx* c, int fd, const char* path, uint8_t di
   }
   (void)hipStreamSynchronize(s);  // no segment copy may still read the pinned buffers
   (void)sd_ws_release(c, s);
-  (void)hipEventDestroy(done[0]);
-  (void)hipEventDestroy(done[1]);
   return rc;
 }
 
@@ -481,13 +385,19 @@ int sd_cas_file_checksum(sd_cas_ctx* c, const char* path, char out_hex[65], int*
   if (rc == SD_CAS_OK && seq) rc = file_checksum_seq(c, fd, path, digest, err_no);
   close(fd);
   if (rc) return rc;
-  static const char* hx = "0123456789abcdef";
-  for (int i = 0; i < 32; i++) { out_hex[2 * i] = hx[digest[i] >> 4]; out_hex[2 * i + 1] = hx[digest[i] & 15]; }
-  out_hex[64] = 0;
+  sd_hex32(digest, out_hex);
   return SD_CAS_OK;
 }
 
 // ---- the validator job over many files -----------------------------------------------
+
+// what the bad flags of classify (bits 1, 4) and of the batch chain (those and its CV list's
+// bound) say
+static const char* batch_bad_message(uint32_t bad) {
+  return (bad & 1) ? "a buffer is longer than 64 GiB"
+                   : (bad & 4) ? "a buffer is misaligned or extends past arena_bytes"
+                               : "the buffers' subtrees exceed arena_bytes' bound (overlapping buffers?)";
+}
 
 int sd_cas_checksums_dev(sd_cas_ctx* c, const void* d_arena, uint64_t arena_bytes,
                          const uint64_t* d_offs, const uint64_t* d_lens, size_t n, uint8_t* d_out,
@@ -510,11 +420,7 @@ int sd_cas_checksums_dev(sd_cas_ctx* c, const void* d_arena, uint64_t arena_byte
   HIP_TRY(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, sd_ws_release(c, s));
   HIP_TRY(c, hipStreamSynchronize(s));
-  if (bad)
-    return fail(c, SD_CAS_EINVAL, "checksums: %s",
-                (bad & 1) ? "a buffer is longer than 64 GiB"
-                          : (bad & 4) ? "a buffer is misaligned or extends past arena_bytes"
-                                      : "the buffers' subtrees exceed arena_bytes' bound (overlapping buffers?)");
+  if (bad) return fail(c, SD_CAS_EINVAL, "checksums: %s", batch_bad_message(bad));
   return SD_CAS_OK;
 }
 
@@ -560,9 +466,7 @@ static int contents_dev(sd_cas_ctx* c, const char* what, const void* d_arena, ui
   HIP_TRY(c, hipStreamSynchronize(s));
   if (verdict[0]) {
     (void)sd_ws_release(c, s);
-    return fail(c, SD_CAS_EINVAL, "%s: %s", what,
-                (verdict[0] & 1) ? "a buffer is longer than 64 GiB"
-                                 : "a buffer is misaligned or extends past arena_bytes");
+    return fail(c, SD_CAS_EINVAL, "%s: %s", what, batch_bad_message(verdict[0]));
   }
   HIP_TRY(c, contents_hash_classified(c, (const uint8_t*)d_arena, d_offs, d_lens, n, verdict[1],
                                       d_keys, s));
@@ -579,8 +483,7 @@ static int contents_dev(sd_cas_ctx* c, const char* what, const void* d_arena, ui
   HIP_TRY(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, sd_ws_release(c, s));
   HIP_TRY(c, hipStreamSynchronize(s));
-  if (bad)
-    return fail(c, SD_CAS_EINVAL, "%s: the buffers' subtrees exceed arena_bytes' bound (overlapping buffers?)", what);
+  if (bad) return fail(c, SD_CAS_EINVAL, "%s: %s", what, batch_bad_message(bad & ~5u));
   return SD_CAS_OK;
 }
 
@@ -599,20 +502,17 @@ int sd_cas_identify_validate_dev(sd_cas_ctx* c, const void* d_arena, uint64_t ar
 }
 
 // file_checksum over many paths.  The batch files are laid out in windows of up to CK_WIN
-// bytes / CK_WIN_FILES files in index order (one slot of up128(st_size + 1) per file: the
-// spare byte shows EOF, so a file that grew since stat fills its slot and is redone by the
-// streaming path), windows rotating over CK_SLOTS pinned + device slots.  Round 6 (VERDICT r5
-// #1): the files are read as PIECES of <= CK_PIECE bytes (1 MiB reads into the pinned slot run
-// faster host-side than one whole-file pread, profiles/r05/official_c/probe_pread.log) taken
-// from ONE queue over the whole job by up to 15 pool threads, while a 16th pool thread pumps:
-// every finished prefix of the current window (>= CK_COPY bytes) goes to HBM as it lands,
-// alternating over two copy streams (one stream moves 8 MiB pieces at ~53 GB/s, two at ~57,
-// profiles/r06/validator/h2d_sizes.log), a finished window gets its header, K3b and its
-// digests back on the compute stream, and a window whose digests are back frees its slot for
-// the readers (the pump reads pieces too when it has nothing to issue).  The pool's threads
-// sit on the GPU's NUMA node (sd_cas_ctx_create).  Warm 2,000-file tmpfs set: 53.5-54.7 GB/s
-// vs 51.6-52.4 with one copy stream and 49.9-53.0 with the pump on the calling thread
-// (profiles/r06/validator/s7_*).  Pinned and device slot layout: offs | lens | digests | data.
+// bytes / CK_WIN_FILES files in index order (one room of up128(st_size + 1) bytes per file:
+// the spare byte shows EOF, so a file that grew since stat fills its room and is redone by the
+// streaming path).  The windows are the units of one piece queue over the whole job
+// (sd_piece_queue.h; round 6): 1 MiB reads into the pinned slot run faster
+// host-side than one whole-file pread (profiles/r05/official_c/probe_pread.log), and one copy
+// stream moves 8 MiB prefixes at ~53 GB/s, two at ~57 (profiles/r06/validator/h2d_sizes.log).
+// A landed window gets its header, K3b and its digests back on the compute stream.  Up to 15
+// readers and the pump run on the pool, which sits on the GPU's NUMA node (sd_cas_ctx_create).
+// Warm 2,000-file tmpfs set: 53.5-54.7 GB/s vs 51.6-52.4 with one copy stream and 49.9-53.0
+// with the pump on the calling thread (profiles/r06/validator/s7_*).  Pinned and device slot
+// layout: offs | lens | digests (| keys) | data.
 //
 // With out_keys (sd_cas_identify_validate_paths) the same read also gives each row's cas part
 // of FileMetadata::new, exactly as sd_cas_file_metadata_from_paths decides it: the stat pass
@@ -629,9 +529,6 @@ static int file_checksums_impl(sd_cas_ctx* c, const char* const* paths, size_t n
   constexpr uint64_t CK_WIN = 128ull << 20;  // data bytes per window
   constexpr uint64_t CK_BIG = CK_WIN / 2;    // larger files stream on their own (64 MiB segments)
   constexpr size_t CK_WIN_FILES = 32768;
-  constexpr uint64_t CK_PIECE = (uint64_t)SD_CK_PIECE_KB << 10;  // read unit (a file's last piece takes the rest)
-  constexpr uint64_t CK_COPY = (uint64_t)SD_CK_COPY_MB << 20;     // H2D unit of a window's landed prefix
-  constexpr int CK_SLOTS = 3;
   const size_t HDR = CK_WIN_FILES * (8 + 8 + 32 + (out_keys ? 8 : 0));
   const size_t SLOT = HDR + CK_WIN + 256;
   enum : uint8_t { K_BATCH = 0, K_STREAM = 1, K_ERROR = 2 };
@@ -665,12 +562,16 @@ static int file_checksums_impl(sd_cas_ctx* c, const char* const* paths, size_t n
     });
   }
   tr.mark("stat");
-  // members (batch files) in index order, grouped into windows; each member's slot offset
-  // and capacity; its pieces in slot byte order (so a prefix of pieces is a prefix of bytes)
-  std::vector<size_t> mfile, wmem{0}, wpiece{0};
-  std::vector<uint64_t> moff, mcap, wbytes;
-  struct Piece { uint32_t mem; uint32_t win; uint64_t off, len; };
-  std::vector<Piece> pieces;
+  // members (batch files) in index order, grouped into windows; each member's offset in the
+  // window's data and its capacity; its pieces in data byte order (so a prefix of pieces is a
+  // prefix of bytes)
+  std::vector<size_t> mfile, wmem{0};
+  std::vector<uint64_t> moff, mcap;
+  std::vector<uint32_t> pmem;  // per piece: its member
+  sdq::Plan pl;
+  pl.slot_bytes = SLOT;
+  pl.data_off = HDR;
+  pl.trace = tr.on;
   {
     uint64_t bytes = 0;
     for (size_t i = 0; i < n; i++) {
@@ -678,253 +579,118 @@ static int file_checksums_impl(sd_cas_ctx* c, const char* const* paths, size_t n
       const uint64_t need = up128(fsize[i] + 1);
       const size_t files = mfile.size() - wmem.back();
       if (files && (bytes + need > CK_WIN || files == CK_WIN_FILES)) {
-        wbytes.push_back(bytes);
+        pl.end_unit(bytes);
         wmem.push_back(mfile.size());
-        wpiece.push_back(pieces.size());
         bytes = 0;
       }
       const uint32_t k = (uint32_t)mfile.size();
       mfile.push_back(i);
       moff.push_back(bytes);
       mcap.push_back(need);
-      const uint64_t np = std::max<uint64_t>(1, need / CK_PIECE);
-      for (uint64_t j = 0; j < np; j++)
-        pieces.push_back({k, (uint32_t)(wmem.size() - 1), j * CK_PIECE,
-                          j + 1 < np ? CK_PIECE : need - j * CK_PIECE});
+      sdq::cut_pieces(need, sdq::PIECE, [&](uint64_t off, uint64_t len) {
+        pl.add_piece(bytes + off, len);
+        pmem.push_back(k);
+      });
       bytes += need;
     }
     if (mfile.size() > wmem.back()) {
-      wbytes.push_back(bytes);
+      pl.end_unit(bytes);
       wmem.push_back(mfile.size());
-      wpiece.push_back(pieces.size());
     }
   }
-  const size_t nw = wbytes.size(), nm = mfile.size(), np = pieces.size();
+  const size_t nw = pl.units(), nm = mfile.size(), np = pl.pieces();
   int rc = SD_CAS_OK;
   if (nw) {
-    if ((rc = ensure_pinned(c, CK_SLOTS * SLOT))) return rc;
-    if ((rc = ensure(c, c->staging, CK_SLOTS * SLOT))) return rc;
+    if ((rc = ensure_pinned(c, pl.slots * SLOT))) return rc;
+    if ((rc = ensure(c, c->staging, pl.slots * SLOT))) return rc;
     size_t wsb = checksum_batch_workspace_bytes(CK_WIN_FILES, CK_WIN);
     if (out_keys) {
       for (size_t w = 0; w < nw; w++) wsb = std::max(wsb, sd_packed_workspace_bytes(c, wmem[w + 1] - wmem[w]));
       if ((rc = ensure(c, c->inplace, inplace_workspace_bytes(CK_WIN_FILES)))) return rc;
     }
     if ((rc = ensure(c, c->ws, wsb))) return rc;
-  }
-  hipStream_t s = c->stream, cs = c->copy;
-  hipEvent_t done[CK_SLOTS] = {}, landed = nullptr;
-  auto destroy_events = [&]() {
-    for (int b = 0; b < CK_SLOTS; b++)
-      if (done[b]) (void)hipEventDestroy(done[b]);
-    if (landed) (void)hipEventDestroy(landed);
-  };
-  for (int b = 0; b < CK_SLOTS && nw; b++)
-    if (hipEventCreateWithFlags(&done[b], hipEventDisableTiming) != hipSuccess) {
-      destroy_events();
-      return fail(c, SD_CAS_EHIP, "file_checksums: event create");
-    }
-  if (nw && hipEventCreateWithFlags(&landed, hipEventDisableTiming) != hipSuccess) {
-    destroy_events();
-    return fail(c, SD_CAS_EHIP, "file_checksums: event create");
-  }
-  // per member: bytes read, read error, and a read that a local regular file never gives (a
-  // short piece before the file's last, or data after a short read)
-  std::unique_ptr<std::atomic<uint64_t>[]> mgot(new std::atomic<uint64_t>[nm]);
-  std::unique_ptr<std::atomic<int>[]> merr(new std::atomic<int>[nm]);
-  std::unique_ptr<std::atomic<uint8_t>[]> mirr(new std::atomic<uint8_t>[nm]);
-  std::unique_ptr<std::atomic<uint8_t>[]> fin(new std::atomic<uint8_t>[np]);
-  for (size_t k = 0; k < nm; k++) { mgot[k].store(0); merr[k].store(0); mirr[k].store(0); }
-  for (size_t p = 0; p < np; p++) fin[p].store(0, std::memory_order_relaxed);
-  std::atomic<size_t> next{0};
-  std::atomic<size_t> freed{0};  // windows [0, freed) have their digests back: their slots are free
-  std::atomic<bool> abort{false};
-  auto slot_free = [&](uint32_t w) { return w < freed.load(std::memory_order_acquire) + CK_SLOTS; };
-  auto read_piece = [&](size_t p) {
-    const Piece& pc = pieces[p];
-    const size_t i = mfile[pc.mem];
-    char* dst = (char*)c->pinned + (size_t)(pc.win % CK_SLOTS) * SLOT + HDR + moff[pc.mem] + pc.off;
-    int fd = open(paths[i], O_RDONLY | O_CLOEXEC);
-    if (fd < 0) {
-      merr[pc.mem].store(errno);
-      return;
-    }
-    uint64_t got = 0;
-    bool was_short = false;
-    while (got < pc.len) {
-      ssize_t r = pread(fd, dst + got, pc.len - got, (off_t)(pc.off + got));
-      if (r < 0 && errno == EINTR) continue;
-      if (r < 0) { merr[pc.mem].store(errno); break; }
-      if (r == 0) break;  // EOF
-      if (was_short) mirr[pc.mem].store(1);  // data after a short read: not a local file
-      if ((uint64_t)r < pc.len - got) was_short = true;
-      got += (uint64_t)r;
-    }
-    close(fd);
-    if (got < pc.len && pc.off + pc.len < mcap[pc.mem]) mirr[pc.mem].store(1);  // ended before its last piece
-    mgot[pc.mem].fetch_add(got);
-  };
-  auto spin = []() {
-#if defined(__x86_64__)
-    __builtin_ia32_pause();
-#else
-    std::this_thread::yield();
-#endif
-  };
-  auto worker = [&]() {
-    for (size_t p; !abort.load(std::memory_order_relaxed) && (p = next.fetch_add(1)) < np;) {
-      // a piece of window w waits for window w - CK_SLOTS to free the slot
-      while (!slot_free(pieces[p].win) && !abort.load(std::memory_order_relaxed)) std::this_thread::yield();
-      if (abort.load(std::memory_order_relaxed)) break;
-      read_piece(p);
-      fin[p].store(1, std::memory_order_release);
-    }
-  };
-  static const char* hx = "0123456789abcdef";
-  auto emit = [&](size_t w) {  // window w's digests are back in its pinned slot: -> hex
-    const uint8_t* dg = (const uint8_t*)c->pinned + (size_t)(w % CK_SLOTS) * SLOT + CK_WIN_FILES * 16;
-    for (size_t k = wmem[w]; k < wmem[w + 1]; k++) {
-      const uint8_t* d = dg + 32 * (k - wmem[w]);
-      char* o = out_hex + 65 * mfile[k];
-      for (int j = 0; j < 32; j++) { o[2 * j] = hx[d[j] >> 4]; o[2 * j + 1] = hx[d[j] & 15]; }
-      o[64] = 0;
-    }
-    if (!out_keys) return;
-    // the window's keys follow its digests; a member whose key is not the window's (khave),
-    // or that has no cas_id, keeps key 0
-    const size_t m = wmem[w + 1] - wmem[w];
-    const uint8_t* kp = dg + 32 * m;
-    for (size_t k = wmem[w]; k < wmem[w + 1]; k++) {
-      const size_t i = mfile[k];
-      if (khave[i] && cas_status[i] == 0) memcpy(&out_keys[i], kp + 8 * (k - wmem[w]), 8);
-    }
-  };
-  uint32_t* d_bad = (uint32_t*)(c->d_scalar + 6);
-  size_t ncopies = 0;
-  double stall_us = 0;
-  // the pump (this thread): copies, window launches, retirement; reads a piece when idle
-  auto pump = [&]() {
-    size_t wc = 0, issued = 0, retired = 0, ready = 0;
-    uint64_t sent = 0;
-    auto hipfail = [&](hipError_t e, const char* what) {
-      rc = fail(c, SD_CAS_EHIP, "file_checksums %s: %s", what, hipGetErrorString(e));
-      abort.store(true);
+    hipStream_t s = c->stream;
+    uint32_t* d_bad = (uint32_t*)(c->d_scalar + 6);
+    QueueDev dev{c, d_bad};
+    if (!dev.ev.ok) return fail(c, SD_CAS_EHIP, "file_checksums: event create");
+    // per member: bytes read, read error, irregular read (all zero-initialised)
+    std::vector<std::atomic<uint64_t>> mgot(nm);
+    std::vector<std::atomic<int>> merr(nm);
+    std::vector<std::atomic<uint8_t>> mirr(nm);
+    auto read = [&](size_t p, size_t at) {
+      const uint32_t k = pmem[p];
+      const uint64_t foff = pl.poff[p] - moff[k];
+      const sdq::ReadResult r =
+          sdq::read_piece(paths[mfile[k]], (char*)c->pinned + at, foff, pl.plen[p], foff + pl.plen[p] < mcap[k]);
+      if (r.err) merr[k].store(r.err);
+      if (r.irregular) mirr[k].store(1);
+      mgot[k].fetch_add(r.got);
     };
-    {
-      hipError_t e = hipSetDevice(c->device);  // (HIP's current device is per thread)
-      if (e == hipSuccess) e = sd_ws_acquire(c, s);
-      if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, 4, s);
-      if (e != hipSuccess) { hipfail(e, "setup"); return; }
-    }
-    while (retired < nw && rc == SD_CAS_OK) {
-      bool progress = false;
-      if (retired < issued) {  // the oldest window in flight: digests back?
-        const hipError_t q = hipEventQuery(done[retired % CK_SLOTS]);
-        if (q == hipSuccess) {
-          emit(retired);
-          freed.store(++retired, std::memory_order_release);
-          continue;
-        }
-        if (q != hipErrorNotReady) { hipfail(q, "window sync"); break; }
+    size_t sampled = 0;  // (pump only) members of the landed window that the contents hash routes to K1P
+    // every piece of window w has landed: decide each member, build and send the header
+    auto landed = [&](size_t w) {
+      char* pin = (char*)c->pinned + (w % pl.slots) * SLOT;
+      uint64_t* h_offs = (uint64_t*)pin;
+      uint64_t* h_lens = h_offs + CK_WIN_FILES;
+      sampled = 0;
+      for (size_t k = wmem[w]; k < wmem[w + 1]; k++) {
+        const size_t i = mfile[k], j = k - wmem[w];
+        h_offs[j] = moff[k];
+        h_lens[j] = 0;  // failed or redone entries are hashed as empty buffers and ignored
+        if (int er = merr[k].load()) { status[i] = -er; kind[i] = K_ERROR; continue; }
+        const uint64_t got = mgot[k].load();
+        // grew past its room, or read unlike a local regular file (a short read before the
+        // end, or an end before st_size): sd_cas_file_checksum afterwards, which reads such a
+        // file exactly as hash.rs:15-21 does (1 MiB reads, stop at the first short one)
+        if (got == mcap[k] || mirr[k].load() || got < fsize[i]) { kind[i] = K_STREAM; continue; }
+        h_lens[j] = got;
+        sampled += got > MINIMUM_FILE_SIZE;
+        // the window's key is le64(got) || what was read: the row's key only when that is
+        // the metadata length too (a procfs file reads past its st_size of 0)
+        if (out_keys && got == fsize[i]) khave[i] = 1;
       }
-      if (wc < nw) {
-        const size_t b = wc % CK_SLOTS;
-        char* pin = (char*)c->pinned + b * SLOT;
-        char* dev = (char*)c->staging.p + b * SLOT;
-        while (ready < wpiece[wc + 1] && fin[ready].load(std::memory_order_acquire)) ++ready;
-        const bool complete = ready == wpiece[wc + 1];
-        const uint64_t hi = complete ? wbytes[wc] : moff[pieces[ready].mem] + pieces[ready].off;
-        if (hi > sent && (hi - sent >= CK_COPY || complete)) {
-          hipStream_t xs = (SD_CK_COPY_STREAMS > 1 && (ncopies & 1)) ? c->copy2 : cs;
-          const hipError_t e = hipMemcpyAsync(dev + HDR + sent, pin + HDR + sent, hi - sent, hipMemcpyHostToDevice, xs);
-          if (e != hipSuccess) { hipfail(e, "copy"); break; }
-          sent = hi;
-          ++ncopies;
-          progress = true;
-        }
-        if (complete && sent == wbytes[wc]) {
-          // every piece of the window has landed: decide each member, header, K3b, digests back
-          uint64_t* h_offs = (uint64_t*)pin;
-          uint64_t* h_lens = h_offs + CK_WIN_FILES;
-          const size_t m = wmem[wc + 1] - wmem[wc];
-          size_t sampled = 0;  // members the contents hash will route to K1P
-          for (size_t k = wmem[wc]; k < wmem[wc + 1]; k++) {
-            const size_t i = mfile[k], j = k - wmem[wc];
-            h_offs[j] = moff[k];
-            h_lens[j] = 0;  // failed or redone entries are hashed as empty buffers and ignored
-            if (int er = merr[k].load()) { status[i] = -er; kind[i] = K_ERROR; continue; }
-            const uint64_t got = mgot[k].load();
-            // grew past its slot, or read unlike a local regular file (a short read before
-            // the end, or an end before st_size): sd_cas_file_checksum afterwards, which reads
-            // such a file exactly as hash.rs:15-21 does (1 MiB reads, stop at the first short one)
-            if (got == mcap[k] || mirr[k].load() || got < fsize[i]) { kind[i] = K_STREAM; continue; }
-            h_lens[j] = got;
-            sampled += got > MINIMUM_FILE_SIZE;
-            // the window's key is le64(got) || what was read: the row's key only when that is
-            // the metadata length too (a procfs file reads past its st_size of 0)
-            if (out_keys && got == fsize[i]) khave[i] = 1;
-          }
-          hipError_t e = hipSuccess;
-          if (SD_CK_COPY_STREAMS > 1) {  // the header copy (on cs) after copy2's pieces too
-            e = hipEventRecord(landed, c->copy2);
-            if (e == hipSuccess) e = hipStreamWaitEvent(cs, landed, 0);
-          }
-          if (e == hipSuccess) e = hipMemcpyAsync(dev, pin, CK_WIN_FILES * 16, hipMemcpyHostToDevice, cs);
-          if (e == hipSuccess) e = hipEventRecord(landed, cs);
-          if (e == hipSuccess) e = hipStreamWaitEvent(s, landed, 0);
-          if (e == hipSuccess)
-            e = checksum_batch_device((const uint8_t*)(dev + HDR), wbytes[wc], (const uint64_t*)dev,
-                                      (const uint64_t*)dev + CK_WIN_FILES, m,
-                                      (uint32_t*)(dev + CK_WIN_FILES * 16), d_bad, c->ws.p, s);
-          if (e == hipSuccess && out_keys) {  // the same buffers' cas keys, after the digests
-            e = inplace_classify(wbytes[wc], (const uint64_t*)dev, (const uint64_t*)dev + CK_WIN_FILES, m,
-                                 c->inplace.p, s);
-            if (e == hipSuccess)
-              e = contents_hash_classified(c, (const uint8_t*)(dev + HDR), (const uint64_t*)dev,
-                                           (const uint64_t*)dev + CK_WIN_FILES, m, sampled,
-                                           (uint64_t*)(dev + CK_WIN_FILES * 16 + m * 32), s);
-          }
-          if (e == hipSuccess)
-            e = hipMemcpyAsync(pin + CK_WIN_FILES * 16, dev + CK_WIN_FILES * 16, m * (out_keys ? 40 : 32),
-                               hipMemcpyDeviceToHost, s);
-          if (e == hipSuccess) e = hipEventRecord(done[b], s);
-          if (e != hipSuccess) { hipfail(e, "window"); break; }
-          ++issued;
-          ++wc;
-          sent = 0;
-          continue;
-        }
-      }
-      if (progress) continue;
-      // nothing to copy or retire: read a piece too (a 16th reader) if its slot is free
-      // (only a piece whose slot is free now: this thread is the one that frees slots)
-      size_t p = next.load(std::memory_order_relaxed);
-      if (SD_CK_PUMP_READS && p < np && slot_free(pieces[p].win) && next.compare_exchange_strong(p, p + 1)) {
-        read_piece(p);
-        fin[p].store(1, std::memory_order_release);
-      } else {
-        const auto t0 = std::chrono::steady_clock::now();
-        spin();
-        if (tr.on) stall_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-      }
-    }
-  };
-  if (nw) {
-#if SD_CK_PUMP_ON_POOL
-    // the pump runs on a pool thread too (bound to the GPU's NUMA node like the readers, see
-    // sd_cas_ctx_create), the calling thread only waits
-    std::atomic<bool> pump_taken{false};
-    const std::function<void()> pool_fn = [&]() {
-      if (!pump_taken.exchange(true)) pump(); else worker();
+      return hipMemcpyAsync((char*)c->staging.p + (w % pl.slots) * SLOT, pin, CK_WIN_FILES * 16,
+                            hipMemcpyHostToDevice, c->copy);
     };
-    c->pool.run2(std::max(2u, std::min(16u, (unsigned)((np + 1) / 2) + 1)), pool_fn, []() {});
-#else
-    c->pool.run2(std::max(1u, std::min(15u, (unsigned)((np + 1) / 2))), worker, pump);
-#endif
+    auto issue = [&](size_t w) {  // K3b, the keys, digests and keys back
+      char* pin = (char*)c->pinned + (w % pl.slots) * SLOT;
+      char* dev_slot = (char*)c->staging.p + (w % pl.slots) * SLOT;
+      const uint64_t* d_offs = (const uint64_t*)dev_slot;
+      const uint64_t* d_lens = d_offs + CK_WIN_FILES;
+      const size_t m = wmem[w + 1] - wmem[w];
+      hipError_t e = checksum_batch_device((const uint8_t*)(dev_slot + HDR), pl.usend[w], d_offs, d_lens, m,
+                                           (uint32_t*)(dev_slot + CK_WIN_FILES * 16), d_bad, c->ws.p, s);
+      if (e == hipSuccess && out_keys) {  // the same buffers' cas keys, after the digests
+        e = inplace_classify(pl.usend[w], d_offs, d_lens, m, c->inplace.p, s);
+        if (e == hipSuccess)
+          e = contents_hash_classified(c, (const uint8_t*)(dev_slot + HDR), d_offs, d_lens, m, sampled,
+                                       (uint64_t*)(dev_slot + CK_WIN_FILES * 16 + m * 32), s);
+      }
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(pin + CK_WIN_FILES * 16, dev_slot + CK_WIN_FILES * 16, m * (out_keys ? 40 : 32),
+                           hipMemcpyDeviceToHost, s);
+      return e;
+    };
+    auto emit = [&](size_t w) {  // window w's digests are back in its pinned slot: -> hex
+      const uint8_t* dg = (const uint8_t*)c->pinned + (w % pl.slots) * SLOT + CK_WIN_FILES * 16;
+      const size_t m = wmem[w + 1] - wmem[w];
+      for (size_t j = 0; j < m; j++) sd_hex32(dg + 32 * j, out_hex + 65 * mfile[wmem[w] + j]);
+      if (!out_keys) return;
+      // the window's keys follow its digests; a member whose key is not the window's (khave),
+      // or that has no cas_id, keeps key 0
+      for (size_t j = 0; j < m; j++) {
+        const size_t i = mfile[wmem[w] + j];
+        if (khave[i] && cas_status[i] == 0) memcpy(&out_keys[i], dg + 32 * m + 8 * j, 8);
+      }
+    };
+    pl.threads = std::max(2u, std::min(16u, (unsigned)((np + 1) / 2) + 1));
+    const sdq::Result res = sdq::run(pl, c->pool, dev, read, landed, issue, emit);
+    if (res.err) rc = queue_failed(c, "file_checksums window", res);
     tr.mark("windows");
     tr.note("windows", (double)nw);
     tr.note("pieces", (double)np);
-    tr.note("copies", (double)ncopies);
-    tr.note("pump_idle_us", stall_us);
+    tr.note("copies", (double)res.copies);
+    tr.note("pump_idle_us", res.pump_idle_us);
     if (tr.on) tr.note("pinned_node", (double)sd_page_node(c->pinned));
     uint32_t bad = 0;
     if (rc == SD_CAS_OK) {
@@ -934,12 +700,7 @@ static int file_checksums_impl(sd_cas_ctx* c, const char* const* paths, size_t n
       else if (bad) rc = fail(c, SD_CAS_EHIP, "file_checksums: batch work list overflow");
     }
     (void)sd_ws_release(c, s);
-    // a failed call leaves nothing in flight that reads the pinned slots
-    (void)hipStreamSynchronize(cs);
-    (void)hipStreamSynchronize(c->copy2);
-    (void)hipStreamSynchronize(s);
   }
-  destroy_events();
   if (rc) return rc;
   // big regular files: 64 MiB segments of all of them in one piece queue, back to back (after
   // the windows: it reuses the pinned and device staging)
@@ -959,9 +720,7 @@ static int file_checksums_impl(sd_cas_ctx* c, const char* const* paths, size_t n
         const size_t i = bi[k];
         if (er[k]) { status[i] = -er[k]; kind[i] = K_ERROR; continue; }
         if (gs[k]) continue;  // read irregularly (or changed since stat): the path below
-        char* o = out_hex + 65 * i;
-        for (int j = 0; j < 32; j++) { o[2 * j] = hx[dg[32 * k + j] >> 4]; o[2 * j + 1] = hx[dg[32 * k + j] & 15]; }
-        o[64] = 0;
+        sd_hex32(&dg[32 * k], out_hex + 65 * i);
         kind[i] = K_BATCH;
       }
     }
