@@ -415,6 +415,72 @@ int sd_cas_identifier_links_ex(sd_cas_ctx* ctx, const uint64_t* h_keys, const ui
                                uint8_t* h_action, uint64_t* h_step_counts, size_t max_steps,
                                uint64_t* out_steps);
 
+/* ---- Object statistics: copies, unique bytes, top duplicate sets -------------------------
+ * What a grouping is worth.  The reference keeps the slot and leaves it empty:
+ * core/src/library/statistics.rs:42,46 writes total_object_count = 0 and total_unique_bytes
+ * = "0" into the `statistics` row (core/prisma/schema.prisma:83,87).  Both are functions of
+ * rep (sd_cas_group_dev: rep[i] = min{ j : key[j] == key[i] }) and sizes (fs::metadata().len()
+ * per row, the array the hash kernels read), which stay on the device.
+ *   head       a row with rep[i] == i: one Object
+ *   valid row  rep[i] <= i and rep[rep[i]] == rep[i]; any other row is BAD: counted in
+ *              SD_CAS_STAT_BAD_ROWS only, copies 0, and its rep is never used as an index
+ *   copies[i]  the number of valid rows j with rep[j] == rep[i] (every member of a set
+ *              carries the set's count)
+ *   waste(h)   (copies[h] - 1) * sizes[h] of a head
+ * Byte sums are u64 (modulo 2^64 should they wrap); no float arithmetic anywhere.
+ * totals[SD_CAS_STAT_COUNT]:
+ *   ROWS valid rows; OBJECTS heads (= statistics.total_object_count, statistics.rs:42 /
+ *   schema.prisma:83); TOTAL_BYTES the valid rows' sizes; UNIQUE_BYTES the heads' sizes
+ *   (= statistics.total_unique_bytes, statistics.rs:46 / schema.prisma:87); DUPLICATE_SETS
+ *   heads with copies >= 2; MAX_COPIES the largest copies (0 without valid rows);
+ *   SIZE_MISMATCH_ROWS valid non-head rows whose size differs from their head's (the size is
+ *   part of the hashed message: a 64-bit key collision or a stale size); BAD_ROWS. */
+#define SD_CAS_STAT_ROWS 0
+#define SD_CAS_STAT_OBJECTS 1
+#define SD_CAS_STAT_TOTAL_BYTES 2
+#define SD_CAS_STAT_UNIQUE_BYTES 3
+#define SD_CAS_STAT_DUPLICATE_SETS 4
+#define SD_CAS_STAT_MAX_COPIES 5
+#define SD_CAS_STAT_SIZE_MISMATCH_ROWS 6
+#define SD_CAS_STAT_BAD_ROWS 7
+#define SD_CAS_STAT_COUNT 8
+#define SD_CAS_TOP_MAX 65536
+/* The values statistics.rs:42,46 leaves at 0 (schema.prisma:83,87), and copies per row.
+ * d_copies (n x u32) is accumulator and output: no workspace of n entries is used.
+ * d_totals (8 x u64, device) may be NULL: a buffer of the context is used.  out_totals NULL:
+ * asynchronous on `stream`.  out_totals given: blocks, fills it, and fails with
+ * SD_CAS_EINVAL (text in sd_cas_last_error) if BAD_ROWS != 0 — out_totals and d_copies are
+ * filled all the same.  n == 0 launches nothing: all-zero totals.  n < 2^32. */
+int sd_cas_object_stats_dev(sd_cas_ctx* ctx, const uint32_t* d_rep, const uint64_t* d_sizes,
+                            size_t n, uint32_t* d_copies, uint64_t* d_totals,
+                            uint64_t out_totals[8], void* stream);
+/* The duplicate sets behind the gap between total_unique_bytes and the library's bytes
+ * (statistics.rs:42,46, schema.prisma:83,87): the found = min(k, DUPLICATE_SETS) heads with
+ * copies >= 2, by waste descending, ties by head ascending, as d_top_heads[j] /
+ * d_top_waste[j]; entries found..k are (SD_CAS_NO_OBJECT, 0).  The order is fully
+ * determined: two runs give identical lists.  d_copies as sd_cas_object_stats_dev left it;
+ * only heads' entries are read and rep is never used as an index, so the call is safe
+ * whatever BAD_ROWS was.  k <= SD_CAS_TOP_MAX (else SD_CAS_EINVAL); k == 0 gives found 0.
+ * Blocking (one small read-back between selection and sort). */
+int sd_cas_top_duplicates_dev(sd_cas_ctx* ctx, const uint32_t* d_rep, const uint64_t* d_sizes,
+                              const uint32_t* d_copies, size_t n, size_t k,
+                              uint32_t* d_top_heads, uint64_t* d_top_waste,
+                              uint64_t* out_found, void* stream);
+/* Grouping, statistics and top list with every array in host memory (the DB layer's side:
+ * the call that fills the columns statistics.rs:42,46 / schema.prisma:83,87 leave at 0).
+ * h_state: SD_CAS_ROW_* per row, NULL = every row hashed.  Only HASHED rows take part: they
+ * are compacted as sd_cas_identifier_links compacts them, grouped with the context's grouping
+ * and scattered back; any other row gets h_rep = SD_CAS_NO_OBJECT and h_copies = 0 (its key
+ * and size are not read).  h_rep and the top heads are indices into the CALLER's row
+ * numbering.  The totals cover hashed rows only: in the reference every NO_CAS row is one
+ * more Object of 0 bytes (mod.rs:246-253), which the caller adds itself.  h_rep, h_copies,
+ * out_totals and the top arrays (both, with out_found) may each be NULL: not wanted.
+ * Blocking; n < 2^32. */
+int sd_cas_duplicate_report(sd_cas_ctx* ctx, const uint64_t* h_keys, const uint64_t* h_sizes,
+                            const uint8_t* h_state, size_t n, uint32_t* h_rep, uint32_t* h_copies,
+                            uint64_t out_totals[8], size_t k, uint32_t* h_top_heads,
+                            uint64_t* h_top_waste, uint64_t* out_found);
+
 /* Stable LSD radix sort of (u64 key, u32 val) on bits [begin_bit, end_bit).
  * d_vals_in == NULL sorts the identity 0..n-1. */
 int sd_cas_sort_pairs_dev(sd_cas_ctx* ctx, const uint64_t* d_keys_in, const uint32_t* d_vals_in,

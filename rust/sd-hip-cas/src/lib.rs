@@ -36,6 +36,16 @@ pub const SD_CAS_LINK_EXISTING: u8 = 4;
 pub const SD_CAS_NO_OBJECT: u32 = 0xFFFF_FFFF;
 pub const SD_CAS_NO_STEP: u32 = 0xFFFF_FFFF;
 pub const SD_CAS_CHUNK_SIZE: u32 = 100;
+pub const SD_CAS_STAT_ROWS: usize = 0;
+pub const SD_CAS_STAT_OBJECTS: usize = 1;
+pub const SD_CAS_STAT_TOTAL_BYTES: usize = 2;
+pub const SD_CAS_STAT_UNIQUE_BYTES: usize = 3;
+pub const SD_CAS_STAT_DUPLICATE_SETS: usize = 4;
+pub const SD_CAS_STAT_MAX_COPIES: usize = 5;
+pub const SD_CAS_STAT_SIZE_MISMATCH_ROWS: usize = 6;
+pub const SD_CAS_STAT_BAD_ROWS: usize = 7;
+pub const SD_CAS_STAT_COUNT: usize = 8;
+pub const SD_CAS_TOP_MAX: usize = 65536;
 /// status of a row whose fs::metadata length is 0: no cas_id (file_identifier/mod.rs:78-86)
 pub const SD_CAS_STATUS_NO_CAS: i32 = 1;
 
@@ -158,6 +168,17 @@ extern "C" {
                                       h_object: *mut u32, h_action: *mut u8,
                                       h_step_counts: *mut u64, max_steps: usize,
                                       out_steps: *mut u64) -> c_int;
+    pub fn sd_cas_object_stats_dev(ctx: *mut sd_cas_ctx, d_rep: *const u32, d_sizes: *const u64,
+                                   n: usize, d_copies: *mut u32, d_totals: *mut u64,
+                                   out_totals: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_cas_top_duplicates_dev(ctx: *mut sd_cas_ctx, d_rep: *const u32, d_sizes: *const u64,
+                                     d_copies: *const u32, n: usize, k: usize,
+                                     d_top_heads: *mut u32, d_top_waste: *mut u64,
+                                     out_found: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_cas_duplicate_report(ctx: *mut sd_cas_ctx, h_keys: *const u64, h_sizes: *const u64,
+                                   h_state: *const u8, n: usize, h_rep: *mut u32, h_copies: *mut u32,
+                                   out_totals: *mut u64, k: usize, h_top_heads: *mut u32,
+                                   h_top_waste: *mut u64, out_found: *mut u64) -> c_int;
     pub fn sd_cas_sort_pairs_dev(ctx: *mut sd_cas_ctx, d_keys_in: *const u64, d_vals_in: *const u32,
                                  n: usize, d_keys_out: *mut u64, d_vals_out: *mut u32, begin_bit: c_int,
                                  end_bit: c_int, stream: *mut c_void) -> c_int;
@@ -282,6 +303,36 @@ pub struct StepBatch {
 pub struct ExistingObject {
     pub cas_id: CasId,
     pub id: u32,
+}
+
+/// One duplicate set of a `Statistics`: its first row, its rows, and the bytes the extra
+/// copies occupy (`(copies - 1) * size`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct DuplicateSet {
+    pub head: usize,
+    pub copies: u32,
+    pub waste: u64,
+}
+
+/// The part of the `statistics` row the reference leaves at 0 (statistics.rs:42,46;
+/// schema.prisma:83,87), over the Hashed rows of a library.  Each `NoCas` row is one more
+/// Object of 0 bytes in the reference (mod.rs:246-253): `no_cas_rows` counts them and
+/// `total_object_count` includes them; `total_unique_bytes` is a string column there.
+#[derive(Clone, Debug, Default, PartialEq, Eq)]
+pub struct Statistics {
+    pub total_object_count: u64,
+    pub total_unique_bytes: u64,
+    pub total_bytes: u64,
+    pub hashed_rows: u64,
+    pub no_cas_rows: u64,
+    pub duplicate_sets: u64,
+    pub max_copies: u64,
+    pub size_mismatch_rows: u64,
+    /// per row: the first row of its Object (`None`: not a Hashed row) and the Object's rows
+    pub object_of: Vec<Option<usize>>,
+    pub copies: Vec<u32>,
+    /// the sets wasting the most space: waste descending, ties by head ascending
+    pub top: Vec<DuplicateSet>,
 }
 
 /// One context per (job thread, device).  Not Sync; Send is fine.
@@ -480,6 +531,51 @@ impl HipCas {
             }
         }
         Ok(out)
+    }
+
+    /// `total_object_count` / `total_unique_bytes` of the `statistics` row (statistics.rs:
+    /// 38-49 writes them as 0) and the `top_k` duplicate sets, from every file_path's state
+    /// and `fs::metadata().len()` — sd_cas_duplicate_report.
+    pub fn statistics(&mut self, rows: &[(RowState, u64)], top_k: usize) -> io::Result<Statistics> {
+        let n = rows.len();
+        let keys: Vec<u64> = rows.iter().map(|(s, _)| if let RowState::Hashed(k) = s { k.0 } else { 0 }).collect();
+        let sizes: Vec<u64> = rows.iter().map(|(_, z)| *z).collect();
+        let state: Vec<u8> = rows
+            .iter()
+            .map(|(s, _)| match s {
+                RowState::Hashed(_) => SD_CAS_ROW_HASHED,
+                RowState::NoCas => SD_CAS_ROW_NO_CAS,
+                RowState::Error => SD_CAS_ROW_ERROR,
+            })
+            .collect();
+        let (mut rep, mut copies) = (vec![0u32; n], vec![0u32; n]);
+        let mut totals = [0u64; SD_CAS_STAT_COUNT];
+        let (mut heads, mut waste) = (vec![0u32; top_k.max(1)], vec![0u64; top_k.max(1)]);
+        let mut found = 0u64;
+        let rc = unsafe {
+            sd_cas_duplicate_report(self.ctx, keys.as_ptr(), sizes.as_ptr(), state.as_ptr(), n,
+                                    rep.as_mut_ptr(), copies.as_mut_ptr(), totals.as_mut_ptr(), top_k,
+                                    heads.as_mut_ptr(), waste.as_mut_ptr(), &mut found)
+        };
+        if rc != 0 {
+            return Err(self.err(rc));
+        }
+        let no_cas = state.iter().filter(|&&s| s == SD_CAS_ROW_NO_CAS).count() as u64;
+        Ok(Statistics {
+            total_object_count: totals[SD_CAS_STAT_OBJECTS] + no_cas,
+            total_unique_bytes: totals[SD_CAS_STAT_UNIQUE_BYTES],
+            total_bytes: totals[SD_CAS_STAT_TOTAL_BYTES],
+            hashed_rows: totals[SD_CAS_STAT_ROWS],
+            no_cas_rows: no_cas,
+            duplicate_sets: totals[SD_CAS_STAT_DUPLICATE_SETS],
+            max_copies: totals[SD_CAS_STAT_MAX_COPIES],
+            size_mismatch_rows: totals[SD_CAS_STAT_SIZE_MISMATCH_ROWS],
+            object_of: rep.iter().map(|&r| (r != SD_CAS_NO_OBJECT).then_some(r as usize)).collect(),
+            top: (0..found as usize)
+                .map(|j| DuplicateSet { head: heads[j] as usize, copies: copies[heads[j] as usize], waste: waste[j] })
+                .collect(),
+            copies,
+        })
     }
 
     /// `file_checksum(path)` (validation/hash.rs:11).

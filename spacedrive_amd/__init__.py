@@ -10,8 +10,12 @@ from .cas import (  # noqa: F401
     SAMPLE_COUNT,
     SAMPLE_SIZE,
     SAMPLED_CONTENT_LEN,
+    STAT_NAMES,
+    TOP_MAX,
+    TOP_TILE,
     CasEngine,
     CasError,
+    DuplicateReport,
     FileMetadata,
     StepResult,
     cas_id_to_key,

@@ -73,6 +73,9 @@ SIGNATURES = [
      [_vp, _vp, _vp, _sz, _u32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("sd_cas_identifier_links_ex", _i,
      [_vp, _vp, _vp, _sz, _u32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    ("sd_cas_object_stats_dev", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("sd_cas_top_duplicates_dev", _i, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+    ("sd_cas_duplicate_report", _i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("sd_cas_sort_pairs_dev", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _i, _i, _vp]),
     ("sd_cas_checksum_dev", _i, [_vp, _vp, _u64, _vp, _vp]),
     ("sd_cas_file_checksum", _i, [_vp, _cp, _cp, ctypes.POINTER(_i)]),

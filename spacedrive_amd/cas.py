@@ -39,6 +39,12 @@ CHUNK_SIZE = 100
 MAX_PACKED_CONTENT_LEN = 104 * 1024 - 8
 THRESHOLD_DEFAULT = (1 << 64) - 1  # SD_CAS_THRESHOLD_DEFAULT
 NO_OBJECT = NO_STEP = 0xFFFFFFFF   # SD_CAS_NO_OBJECT / SD_CAS_NO_STEP
+# SD_CAS_STAT_* in index order (the keys of the totals dicts), SD_CAS_TOP_MAX, and the tile of
+# the top list's stable compaction (object_stats.hip: TOP_THREADS x TOP_ITEMS rows)
+STAT_NAMES = ("rows", "objects", "total_bytes", "unique_bytes", "duplicate_sets", "max_copies",
+              "size_mismatch_rows", "bad_rows")
+TOP_MAX = 65536
+TOP_TILE = 16384
 
 
 def key_to_cas_id(key: int) -> str:
@@ -124,6 +130,18 @@ def _path_array(paths: Sequence) -> tuple[object, int]:
             return (buf, cbuf, ptrs), _np_ptr(ptrs)
     parr = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(p) for p in paths])
     return parr, ctypes.cast(parr, ctypes.c_void_p).value
+
+
+@dataclass
+class DuplicateReport:
+    """sd_cas_duplicate_report: rep / copies per row in the caller's numbering (NO_OBJECT / 0
+    on rows that are not hashed), the totals keyed by STAT_NAMES, and the top list (k entries,
+    (NO_OBJECT, 0) past the sets found)."""
+    rep: np.ndarray
+    copies: np.ndarray
+    totals: dict
+    top_heads: np.ndarray
+    top_waste: np.ndarray
 
 
 class CasEngine:
@@ -513,6 +531,75 @@ class CasEngine:
             "identifier_links")
         s = int(steps.value)
         return step, obj, act, counts[:2 * s].reshape(s, 2).astype(np.int64)
+
+    def object_stats(self, rep, sizes, copies, totals=None, stream: Optional[int] = None,
+                     want_totals: bool = True) -> Optional[dict]:
+        """sd_cas_object_stats_dev: copies[i] (int32 device tensor, accumulator and output) =
+        the rows of row i's Object, and the eight totals of a grouping `rep` (as group) with
+        the rows' sizes — total_object_count and total_unique_bytes of the reference's
+        `statistics` row (statistics.rs:42,46) among them.  totals: None or an int64 [8]
+        device tensor.  want_totals blocks and returns the totals keyed by STAT_NAMES (raises
+        EINVAL if rep holds bad rows); otherwise the call is asynchronous and returns None."""
+        import torch
+        n = int(rep.numel())
+        _check_dev(rep, (torch.int32, torch.uint32), n, "rep")
+        _check_dev(sizes, (torch.int64, torch.uint64), n, "sizes")
+        _check_dev(copies, (torch.int32, torch.uint32), n, "copies")
+        if totals is not None:
+            _check_dev(totals, (torch.int64, torch.uint64), len(STAT_NAMES), "totals")
+        out = np.zeros(len(STAT_NAMES), dtype=np.uint64)
+        self._check(self.L.sd_cas_object_stats_dev(
+            self.h, _ptr(rep), _ptr(sizes), n, _ptr(copies),
+            _ptr(totals) if totals is not None else None,
+            _np_ptr(out) if want_totals else None, _stream(stream)), "object_stats")
+        return {k: int(v) for k, v in zip(STAT_NAMES, out)} if want_totals else None
+
+    def top_duplicates(self, rep, sizes, copies, k: int, heads, waste,
+                       stream: Optional[int] = None) -> int:
+        """sd_cas_top_duplicates_dev: the min(k, duplicate sets) heads with copies >= 2 by
+        waste = (copies - 1) * size descending, ties by head ascending, into heads (int32 [k])
+        / waste (int64 [k]) device tensors; the rest is (NO_OBJECT, 0).  Returns the number
+        found.  copies as object_stats left it.  Blocking; k <= TOP_MAX."""
+        import torch
+        n = int(rep.numel())
+        k = int(k)
+        _check_dev(rep, (torch.int32, torch.uint32), n, "rep")
+        _check_dev(sizes, (torch.int64, torch.uint64), n, "sizes")
+        _check_dev(copies, (torch.int32, torch.uint32), n, "copies")
+        if k <= TOP_MAX:  # a larger k is the library's EINVAL, whatever the arrays hold
+            _check_dev(heads, (torch.int32, torch.uint32), k, "heads")
+            _check_dev(waste, (torch.int64, torch.uint64), k, "waste")
+        found = ctypes.c_uint64(0)
+        self._check(self.L.sd_cas_top_duplicates_dev(
+            self.h, _ptr(rep), _ptr(sizes), _ptr(copies), n, k, _ptr(heads), _ptr(waste),
+            ctypes.byref(found), _stream(stream)), "top_duplicates")
+        return int(found.value)
+
+    def duplicate_report(self, keys, sizes, state=None, k: int = 0) -> DuplicateReport:
+        """sd_cas_duplicate_report (host arrays, the DB layer's side): grouping, copies,
+        totals and the top-k duplicate sets of the HASHED rows (state: ROW_* per row, None =
+        all hashed), everything in the caller's row numbering."""
+        n = len(keys)
+        kk = np.ascontiguousarray(keys, dtype=np.uint64)
+        sz = _sizes_u64(sizes)
+        if sz.shape != (n,):
+            raise ValueError(f"sizes has shape {sz.shape}, expected ({n},)")
+        st = None if state is None else np.ascontiguousarray(state, dtype=np.uint8)
+        if st is not None and st.shape != (n,):
+            raise ValueError(f"state has shape {st.shape}, expected ({n},)")
+        k = int(k)
+        rep = np.zeros(n, dtype=np.uint32)
+        copies = np.zeros(n, dtype=np.uint32)
+        totals = np.zeros(len(STAT_NAMES), dtype=np.uint64)
+        heads = np.zeros(max(k, 1), dtype=np.uint32)
+        waste = np.zeros(max(k, 1), dtype=np.uint64)
+        found = ctypes.c_uint64(0)
+        self._check(self.L.sd_cas_duplicate_report(
+            self.h, _np_ptr(kk), _np_ptr(sz), _np_ptr(st) if st is not None else None, n,
+            _np_ptr(rep), _np_ptr(copies), _np_ptr(totals), k, _np_ptr(heads), _np_ptr(waste),
+            ctypes.byref(found)), "duplicate_report")
+        return DuplicateReport(rep, copies, {q: int(v) for q, v in zip(STAT_NAMES, totals)},
+                               heads[:k], waste[:k])
 
     def keys_to_hex(self, keys, out, stream: Optional[int] = None) -> None:
         """The cas_id column of a device batch: out (uint8, 16 per key, 16-B aligned)."""

@@ -34,6 +34,7 @@
 #include "sd_kernels.h"
 #include "sd_links.h"
 #include "sd_mix.h"
+#include "sd_object_stats.h"
 #include "sd_synth.h"
 
 using namespace sdcas;
@@ -46,12 +47,14 @@ uint32_t sd_dbg_violations_group();
 uint32_t sd_dbg_violations_checksum();
 uint32_t sd_dbg_violations_links();
 uint32_t sd_dbg_violations_inplace();
+uint32_t sd_dbg_violations_object_stats();
 }  // namespace sdcas
 // debug library only (libsd_hip_cas_debug.so, not in the ABI header): invariant violations
 // counted by the device checks of sd_debug.h since the library was loaded
 extern "C" uint64_t sd_cas_debug_violations(void) {
   return (uint64_t)sd_dbg_violations_group_hash() + sd_dbg_violations_group() +
-         sd_dbg_violations_checksum() + sd_dbg_violations_links() + sd_dbg_violations_inplace();
+         sd_dbg_violations_checksum() + sd_dbg_violations_links() + sd_dbg_violations_inplace() +
+         sd_dbg_violations_object_stats();
 }
 #endif
 
@@ -883,6 +886,217 @@ int sd_cas_identifier_links(sd_cas_ctx* c, const uint64_t* h_keys, const uint8_t
                             uint64_t* out_steps) {
   return sd_cas_identifier_links_seeded(c, h_keys, h_state, n, chunk, nullptr, nullptr, 0, h_step,
                                         h_object, h_action, h_step_counts, max_steps, out_steps);
+}
+
+// ---- Object statistics -----------------------------------------------------------------
+// statistics.rs:42,46 writes total_object_count and total_unique_bytes as 0 (schema.prisma:
+// 83,87): object_stats.hip fills them from rep and sizes.
+
+static_assert(SD_CAS_STAT_ROWS == STAT_ROWS && SD_CAS_STAT_OBJECTS == STAT_OBJECTS &&
+                  SD_CAS_STAT_TOTAL_BYTES == STAT_TOTAL_BYTES &&
+                  SD_CAS_STAT_UNIQUE_BYTES == STAT_UNIQUE_BYTES &&
+                  SD_CAS_STAT_DUPLICATE_SETS == STAT_DUPLICATE_SETS &&
+                  SD_CAS_STAT_MAX_COPIES == STAT_MAX_COPIES &&
+                  SD_CAS_STAT_SIZE_MISMATCH_ROWS == STAT_SIZE_MISMATCH_ROWS &&
+                  SD_CAS_STAT_BAD_ROWS == STAT_BAD_ROWS && SD_CAS_STAT_COUNT == STAT_COUNT,
+              "stat constants");
+
+// ws: totals shards | the context's totals (d_totals NULL).  state: the host form's row
+// states (rows that are not hashed take no part).
+static int object_stats_impl(sd_cas_ctx* c, const uint32_t* d_rep, const uint64_t* d_sizes,
+                             const uint8_t* d_state, size_t n, uint32_t* d_copies,
+                             uint64_t* d_totals, uint64_t* out_totals, hipStream_t s) {
+  if (n == 0) {
+    if (d_totals) HIP_TRY(c, hipMemsetAsync(d_totals, 0, SD_CAS_STAT_COUNT * 8, s));
+    if (out_totals) {
+      for (int k = 0; k < SD_CAS_STAT_COUNT; k++) out_totals[k] = 0;
+      if (d_totals) HIP_TRY(c, hipStreamSynchronize(s));
+    }
+    return SD_CAS_OK;
+  }
+  const size_t b_sh = up256(stats_shard_bytes());
+  int rc = ensure(c, c->ws, b_sh + 256);
+  if (rc) return rc;
+  uint64_t* shards = (uint64_t*)c->ws.p;
+  if (!d_totals) d_totals = (uint64_t*)((char*)c->ws.p + b_sh);
+  HIP_TRY(c, sd_ws_acquire(c, s));
+  HIP_TRY(c, object_stats(d_rep, d_sizes, d_state, n, d_copies, d_totals, shards, s));
+  if (out_totals)
+    HIP_TRY(c, hipMemcpyAsync(out_totals, d_totals, SD_CAS_STAT_COUNT * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, sd_ws_release(c, s));
+  if (out_totals) {
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (out_totals[SD_CAS_STAT_BAD_ROWS])
+      return fail(c, SD_CAS_EINVAL,
+                  "object_stats: %llu rows whose rep is not a grouping (rep[i] > i or rep[rep[i]] != rep[i])",
+                  (unsigned long long)out_totals[SD_CAS_STAT_BAD_ROWS]);
+  }
+  return SD_CAS_OK;
+}
+
+int sd_cas_object_stats_dev(sd_cas_ctx* c, const uint32_t* d_rep, const uint64_t* d_sizes, size_t n,
+                            uint32_t* d_copies, uint64_t* d_totals, uint64_t out_totals[8],
+                            void* stream) {
+  if (!c) return SD_CAS_EINVAL;
+  if (n >= (1ull << 32) || (n && (!d_rep || !d_sizes || !d_copies)))
+    return fail(c, SD_CAS_EINVAL, "object_stats: bad arguments");
+  return object_stats_impl(c, d_rep, d_sizes, nullptr, n, d_copies, d_totals, out_totals,
+                           pick(c, stream));
+}
+
+int sd_cas_top_duplicates_dev(sd_cas_ctx* c, const uint32_t* d_rep, const uint64_t* d_sizes,
+                              const uint32_t* d_copies, size_t n, size_t k, uint32_t* d_top_heads,
+                              uint64_t* d_top_waste, uint64_t* out_found, void* stream) {
+  if (!c) return SD_CAS_EINVAL;
+  if (!out_found || n >= (1ull << 32) || (n && (!d_rep || !d_sizes || !d_copies)) ||
+      (k && (!d_top_heads || !d_top_waste)))
+    return fail(c, SD_CAS_EINVAL, "top_duplicates: bad arguments");
+  if (k > SD_CAS_TOP_MAX)
+    return fail(c, SD_CAS_EINVAL, "top_duplicates: k = %zu exceeds SD_CAS_TOP_MAX", k);
+  *out_found = 0;
+  if (k == 0) return SD_CAS_OK;
+  hipStream_t s = pick(c, stream);
+  if (n == 0) {
+    HIP_TRY(c, top_write(nullptr, nullptr, 0, k, d_top_heads, d_top_waste, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return SD_CAS_OK;
+  }
+  // ws: histogram | selection words | tile counts and offsets | candidates (~waste, head) | sorted
+  // candidates | the sort's workspace.  The candidate count m is known only after the
+  // selection, so the first part is sized up front; if the rest does not fit, ws grows (that
+  // synchronises and drops its contents) and the selection runs once more — the steady state
+  // is one 32-byte read-back, the call's one sync before the final one.
+  const size_t b_hist = up256(TOP_BINS * 8), b_sel = up256(TOP_SEL_WORDS * 8),
+               b_off = up256(top_scan_bytes(n)), b_small = b_hist + b_sel + b_off;
+  int rc = ensure(c, c->ws, b_small);
+  if (rc) return rc;
+  HIP_TRY(c, sd_ws_acquire(c, s));
+  uint64_t sel[TOP_SEL_WORDS] = {0, 0, 0, 0};
+  {
+    char* p = (char*)c->ws.p;
+    uint64_t* d_sel = (uint64_t*)(p + b_hist);
+    HIP_TRY(c, top_select(d_rep, d_sizes, d_copies, n, k, (uint64_t*)p, d_sel,
+                          (uint32_t*)(p + b_hist + b_sel), s));
+    HIP_TRY(c, hipMemcpyAsync(sel, d_sel, sizeof sel, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+  }
+  const uint64_t m = sel[TOP_SEL_M];
+  const int top_bin = (int)sel[TOP_SEL_TOP];
+  const size_t b_k = up256(m * 8), b_v = up256(m * 4);
+  const size_t need = b_small + 2 * (b_k + b_v) + (m ? sort_workspace_bytes(m) : 0);
+  if (need > c->ws.bytes) {
+    if ((rc = ensure(c, c->ws, need))) return rc;
+    char* p = (char*)c->ws.p;
+    HIP_TRY(c, top_select(d_rep, d_sizes, d_copies, n, k, (uint64_t*)p, (uint64_t*)(p + b_hist),
+                          (uint32_t*)(p + b_hist + b_sel), s));
+  }
+  char* p = (char*)c->ws.p;
+  const uint64_t* d_sel = (const uint64_t*)(p + b_hist);
+  const uint32_t* scan = (const uint32_t*)(p + b_hist + b_sel);
+  p += b_small;
+  uint64_t* ckeys = (uint64_t*)p; p += b_k;
+  uint32_t* cvals = (uint32_t*)p; p += b_v;
+  uint64_t* skeys = (uint64_t*)p; p += b_k;
+  uint32_t* svals = (uint32_t*)p; p += b_v;
+  const uint64_t found = std::min<uint64_t>(k, m);
+  if (m) {
+    HIP_TRY(c, top_emit(d_rep, d_sizes, d_copies, n, d_sel, scan, ckeys, cvals, s));
+    // every candidate's waste is below 2^top_bin, so ~waste differs in bits [0, top_bin) only
+    if (m > 1 && top_bin > 0) {
+      HIP_TRY(c, radix_sort_pairs(ckeys, cvals, skeys, svals, m, 0, top_bin, p, s));
+    } else {
+      skeys = ckeys;
+      svals = cvals;
+    }
+  }
+  HIP_TRY(c, top_write(skeys, svals, found, k, d_top_heads, d_top_waste, s));
+  HIP_TRY(c, sd_ws_release(c, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  *out_found = found;
+  return SD_CAS_OK;
+}
+
+int sd_cas_duplicate_report(sd_cas_ctx* c, const uint64_t* h_keys, const uint64_t* h_sizes,
+                            const uint8_t* h_state, size_t n, uint32_t* h_rep, uint32_t* h_copies,
+                            uint64_t out_totals[8], size_t k, uint32_t* h_top_heads,
+                            uint64_t* h_top_waste, uint64_t* out_found) {
+  if (!c) return SD_CAS_EINVAL;
+  const bool want_top = h_top_heads && h_top_waste;
+  if (n >= (1ull << 32) || (n && (!h_keys || !h_sizes)) || (!h_top_heads != !h_top_waste) ||
+      (want_top && !out_found))
+    return fail(c, SD_CAS_EINVAL, "duplicate_report: bad arguments");
+  if (want_top && k > SD_CAS_TOP_MAX)
+    return fail(c, SD_CAS_EINVAL, "duplicate_report: k = %zu exceeds SD_CAS_TOP_MAX", k);
+  if (out_found) *out_found = 0;
+  if (out_totals)
+    for (int j = 0; j < SD_CAS_STAT_COUNT; j++) out_totals[j] = 0;
+  if (n == 0) {
+    if (want_top)
+      for (size_t j = 0; j < k; j++) { h_top_heads[j] = SD_CAS_NO_OBJECT; h_top_waste[j] = 0; }
+    return SD_CAS_OK;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  // device copies (c->io): keys | sizes | state | rep | copies | hashed keys | hashed rows |
+  // their minimum rows | orphan list | top heads | top waste | 2 counters
+  const size_t b8 = up256(n * 8), b4 = up256(n * 4), b1 = up256(n);
+  const size_t kk = want_top ? k : 0, bth = up256(kk * 4), btw = up256(kk * 8);
+  const size_t bst = h_state ? b1 + b8 + 2 * b4 + b8 : 0;
+  int rc = ensure(c, c->io, 2 * b8 + 2 * b4 + bst + bth + btw + 256);
+  if (rc) return rc;
+  char* p = (char*)c->io.p;
+  uint64_t* d_keys = (uint64_t*)p; p += b8;
+  uint64_t* d_sizes = (uint64_t*)p; p += b8;
+  uint32_t* d_rep = (uint32_t*)p; p += b4;
+  uint32_t* d_copies = (uint32_t*)p; p += b4;
+  uint8_t* d_state = nullptr;
+  uint64_t *hkeys = nullptr, *orphans = nullptr;
+  uint32_t *hrows = nullptr, *minrow = nullptr;
+  if (h_state) {
+    d_state = (uint8_t*)p; p += b1;
+    hkeys = (uint64_t*)p; p += b8;
+    hrows = (uint32_t*)p; p += b4;
+    minrow = (uint32_t*)p; p += b4;
+    orphans = (uint64_t*)p; p += b8;
+  }
+  uint32_t* d_th = (uint32_t*)p; p += bth;
+  uint64_t* d_tw = (uint64_t*)p; p += btw;
+  uint64_t* counters = (uint64_t*)p;
+  hipStream_t s = c->stream;
+  HIP_TRY(c, hipMemcpyAsync(d_keys, h_keys, n * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(d_sizes, h_sizes, n * 8, hipMemcpyHostToDevice, s));
+  if (h_state) {
+    // the hashed rows compacted as (key, row) pairs, grouped by the minimum row per key and
+    // scattered back: rep in the CALLER's numbering, SD_CAS_NO_OBJECT on every other row
+    uint64_t cnt[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(d_state, h_state, n, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(counters, 0, 16, s));
+    HIP_TRY(c, hipMemsetAsync(d_rep, 0xFF, n * 4, s));
+    HIP_TRY(c, links_split(d_keys, d_state, n, hkeys, hrows, counters, orphans, counters + 1, 0u, s));
+    HIP_TRY(c, hipMemcpyAsync(cnt, counters, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (cnt[0]) {
+      if ((rc = sd_cas_group_min_dev(c, hkeys, hrows, cnt[0], minrow, nullptr, s))) return rc;
+      HIP_TRY(c, links_scatter(minrow, hrows, cnt[0], d_rep, 0u, s));
+    }
+  } else {
+    if ((rc = sd_cas_group_dev(c, d_keys, n, d_rep, nullptr, s))) return rc;
+  }
+  uint64_t totals[SD_CAS_STAT_COUNT];
+  if ((rc = object_stats_impl(c, d_rep, d_sizes, d_state, n, d_copies, nullptr, totals, s))) return rc;
+  if (out_totals)
+    for (int j = 0; j < SD_CAS_STAT_COUNT; j++) out_totals[j] = totals[j];
+  if (want_top) {
+    if ((rc = sd_cas_top_duplicates_dev(c, d_rep, d_sizes, d_copies, n, k, d_th, d_tw, out_found, s)))
+      return rc;
+    if (k) {
+      HIP_TRY(c, hipMemcpyAsync(h_top_heads, d_th, k * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(c, hipMemcpyAsync(h_top_waste, d_tw, k * 8, hipMemcpyDeviceToHost, s));
+    }
+  }
+  if (h_rep) HIP_TRY(c, hipMemcpyAsync(h_rep, d_rep, n * 4, hipMemcpyDeviceToHost, s));
+  if (h_copies) HIP_TRY(c, hipMemcpyAsync(h_copies, d_copies, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  return SD_CAS_OK;
 }
 
 // ---- synthetic inputs ----------------------------------------------------------------
