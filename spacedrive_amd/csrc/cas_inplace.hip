@@ -27,6 +27,7 @@
 #include "sd_inplace_plan.h"
 #include "sd_kernels.h"
 #include "sd_segment_merge.h"
+#include "sd_ws.h"
 
 namespace sdcas {
 
@@ -180,22 +181,22 @@ sd_cas_inplace_kernel(const uint8_t* __restrict__ arena, const uint64_t* __restr
 
 // ---- host launchers -------------------------------------------------------------------------
 // workspace: counters (256 B) | lens32 [n] | sampled_idx [n]
-size_t inplace_workspace_bytes(uint64_t n) { return 256 + 2 * ((n * 4 + 255) & ~(uint64_t)255); }
-uint32_t* inplace_counters(void* ws) { return (uint32_t*)ws; }
-uint32_t* inplace_lens32(void* ws) { return (uint32_t*)((char*)ws + 256); }
-uint32_t* inplace_sampled_idx(void* ws, uint64_t n) {
-  return (uint32_t*)((char*)ws + 256 + ((n * 4 + 255) & ~(uint64_t)255));
+InplaceWs inplace_layout(void* ws, uint64_t n) {
+  WsCarve w(ws);  InplaceWs L;
+  L.counters = w.take<uint32_t>(64);  L.lens32 = w.take<uint32_t>(n);  L.sampled_idx = w.take<uint32_t>(n);
+  L.bytes = w.bytes();  return L;
 }
+size_t inplace_workspace_bytes(uint64_t n) { return inplace_layout(nullptr, n).bytes; }
 
 hipError_t inplace_classify(uint64_t arena_bytes, const uint64_t* offs, const uint64_t* lens,
                             uint64_t n, void* ws, hipStream_t s) {
   if (n == 0) return hipSuccess;
   if (n >= (1ull << 32)) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(inplace_counters(ws), 0, 8, s);
+  const InplaceWs L = inplace_layout(ws, n);
+  hipError_t e = hipMemsetAsync(L.counters, 0, 8, s);
   if (e != hipSuccess) return e;
   sd_cas_inplace_classify<<<(uint32_t)((n + 255) / 256), 256, 0, s>>>(
-      offs, lens, n, arena_bytes, inplace_lens32(ws), inplace_sampled_idx(ws, n),
-      inplace_counters(ws));
+      offs, lens, n, arena_bytes, L.lens32, L.sampled_idx, L.counters);
   return hipGetLastError();
 }
 

@@ -20,6 +20,7 @@
 #include "sd_checksum.h"
 #include "sd_debug.h"
 #include "sd_group.h"
+#include "sd_ws.h"
 
 #include <algorithm>
 
@@ -894,8 +895,6 @@ hipError_t checksum_single_setup(uint64_t* d_ol, uint64_t len, uint32_t* d_bad, 
   return hipGetLastError();
 }
 
-static inline size_t al256c(size_t x) { return (x + 255) / 256 * 256; }
-
 SD_DBG_ACCESSOR(sd_dbg_violations_checksum)
 
 // work items of the big-buffer list: <= n + arena_bytes / 1 MiB (disjoint buffers)
@@ -905,14 +904,23 @@ static inline uint64_t batch_items_cap(uint64_t n, uint64_t arena_bytes) {
 
 static inline bool lane_path(uint64_t n) { return n >= LANE_MIN_BUFFERS; }
 
+// groups | gstart | scan partials | group total (u64) | owner | cvs [| LaneInfo counters | lane keys |
+// sorted keys | order | sort ws]: without the lane path these are null and take no room
+ChecksumBatchWs checksum_batch_layout(void* ws, uint64_t n, uint64_t arena_bytes) {
+  const uint64_t items = batch_items_cap(n, arena_bytes), ln = lane_path(n) ? n : 0;
+  WsCarve w(ws);  ChecksumBatchWs L;
+  L.groups = w.take<uint32_t>(n + 1);  L.gstart = w.take<uint32_t>(n + 1);
+  L.partial = w.take<uint32_t>(n / 4096 + 2);  L.gtotal = w.take<unsigned long long>(1);
+  L.owner = w.take<uint32_t>(items);  L.cvs = w.take<uint32_t>(items * 8);
+  L.lane_info = ln ? w.take<uint32_t>(64) : nullptr;  // (zeroed by the count kernel)
+  L.lkeys = ln ? w.take<uint64_t>(ln) : nullptr;  L.skeys = ln ? w.take<uint64_t>(ln) : nullptr;
+  L.order = ln ? w.take<uint32_t>(ln) : nullptr;
+  L.sort_ws = w.nest(ln ? sort_workspace_bytes(ln) : 0);
+  w.skip(256);  // reserve nobody reads
+  L.bytes = w.bytes();  return L;
+}
 size_t checksum_batch_workspace_bytes(uint64_t n, uint64_t arena_bytes) {
-  // groups | gstart | scan partials | group total (u64) | owner | cvs
-  //   [| lane class total | lane keys | sorted keys | order | sort ws]
-  const uint64_t items = batch_items_cap(n, arena_bytes);
-  size_t b = 2 * al256c((n + 1) * 4) + al256c((n / 4096 + 2) * 4) + 256 + al256c(items * 4) +
-             al256c(items * 32);
-  if (lane_path(n)) b += 256 + 2 * al256c(n * 8) + al256c(n * 4) + sort_workspace_bytes(n);
-  return b + 256;
+  return checksum_batch_layout(nullptr, n, arena_bytes).bytes;
 }
 
 hipError_t checksum_batch_device(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* offs,
@@ -923,60 +931,57 @@ hipError_t checksum_batch_device(const uint8_t* arena, uint64_t arena_bytes, con
   const uint64_t items = batch_items_cap(n, arena_bytes);
   // item indices (owner, gstart) are u32: an arena past 4 PiB is refused
   if (items > 0xFFFFFFFFull) return hipErrorInvalidValue;
-  char* p = (char*)ws;
-  uint32_t* groups = (uint32_t*)p; p += al256c((n + 1) * 4);
-  uint32_t* gstart = (uint32_t*)p; p += al256c((n + 1) * 4);
-  uint32_t* partial = (uint32_t*)p; p += al256c((n / 4096 + 2) * 4);
-  unsigned long long* gtotal = (unsigned long long*)p; p += 256;
-  uint32_t* owner = (uint32_t*)p; p += al256c(items * 4);
-  uint32_t* cvs = (uint32_t*)p; p += al256c(items * 32);
-  const bool lane = lane_path(n);
-  uint32_t* lane_info = nullptr;  // LaneInfo counters (zeroed by the count kernel)
-  uint32_t* order = nullptr;
-  if (lane) { lane_info = (uint32_t*)p; p += 256; }
+  const ChecksumBatchWs L = checksum_batch_layout(ws, n, arena_bytes);
   const uint32_t nb = (uint32_t)((n + 255) / 256);
-  sd_b3_batch_count<<<nb, 256, 0, s>>>(offs, lens, n, arena_bytes, groups, d_bad, lane_info);
-  hipError_t e = exclusive_scan_u32(groups, gstart, n, partial, s, gtotal);
+  sd_b3_batch_count<<<nb, 256, 0, s>>>(offs, lens, n, arena_bytes, L.groups, d_bad, L.lane_info);
+  hipError_t e = exclusive_scan_u32(L.groups, L.gstart, n, L.partial, s, L.gtotal);
   if (e != hipSuccess) return e;
   sd_b3_batch_owner<<<(uint32_t)std::min<uint64_t>((items + 255) / 256, 2048), 256, 0, s>>>(
-      gstart, gtotal, n, items, owner);
-  if (lane) {
+      L.gstart, L.gtotal, n, items, L.owner);
+  if (lane_path(n)) {
     // buffers of <= lane_cut() chunks one per lane, by descending chunk count
-    uint64_t* lkeys = (uint64_t*)p; p += al256c(n * 8);
-    uint64_t* skeys = (uint64_t*)p; p += al256c(n * 8);
-    order = (uint32_t*)p; p += al256c(n * 4);
     const bool block_key = arena_bytes <= n * LANE_BLOCK_KEY_MEAN;
     sd_b3_lane_keys<<<std::min<uint32_t>(nb, 1024), 256, 0, s>>>(offs, lens, n, arena_bytes,
-                                                               block_key ? 1 : 0, lkeys, lane_info);
-    e = radix_sort_pairs(lkeys, nullptr, skeys, order, n, 0,
-                         block_key ? LANE_KEY_BITS_BLOCKS : LANE_KEY_BITS_CHUNKS, p, s);
+                                                               block_key ? 1 : 0, L.lkeys, L.lane_info);
+    e = radix_sort_pairs(L.lkeys, nullptr, L.skeys, L.order, n, 0,
+                         block_key ? LANE_KEY_BITS_BLOCKS : LANE_KEY_BITS_CHUNKS, L.sort_ws, s);
     if (e != hipSuccess) return e;
     sd_b3_batch_lane<<<(uint32_t)((n + LANE_BLOCK - 1) / LANE_BLOCK), LANE_BLOCK, LANE_LDS_PAD, s>>>(
-        arena, arena_bytes, offs, lens, order, n, lane_info, d_digests);
+        arena, arena_bytes, offs, lens, L.order, n, L.lane_info, d_digests);
   }
   // small buffers (those the lane kernel does not take): <= 16 chunks four per wave, 17..64
   // chunks one per wave (up to 8 workgroups of 4 waves per CU); then 65..256 chunks
   sd_b3_batch_small16<<<(uint32_t)std::min<uint64_t>((n + 15) / 16, 256 * 8), 256, 0, s>>>(
-      arena, arena_bytes, offs, lens, n, order, lane_info, d_digests);
+      arena, arena_bytes, offs, lens, n, L.order, L.lane_info, d_digests);
   sd_b3_batch_small64<<<(uint32_t)std::min<uint64_t>((n + 3) / 4, 256 * 8), 256, 0, s>>>(
-      arena, arena_bytes, offs, lens, n, order, lane_info, d_digests);
+      arena, arena_bytes, offs, lens, n, L.order, L.lane_info, d_digests);
   sd_b3_batch_mid<<<(uint32_t)std::min<uint64_t>((n + 3) / 4, 256 * 8), 256, 0, s>>>(
-      arena, arena_bytes, offs, lens, n, order, lane_info, d_digests);
+      arena, arena_bytes, offs, lens, n, L.order, L.lane_info, d_digests);
   // big buffers: a grid of up to 65,536 workgroups strides over the item list (those past
   // the list's end exit at once)
   sd_b3_batch_groups<<<(uint32_t)std::min<uint64_t>(items, 65536), GROUP, 0, s>>>(
-      arena, offs, lens, gstart, groups, owner, gtotal, n, items, cvs, d_digests, d_bad);
+      arena, offs, lens, L.gstart, L.groups, L.owner, L.gtotal, n, items, L.cvs, d_digests, d_bad);
   sd_b3_batch_blocks<<<(uint32_t)((items + GROUP - 1) / GROUP), GROUP, 0, s>>>(
-      gstart, groups, owner, gtotal, n, items, cvs);
+      L.gstart, L.groups, L.owner, L.gtotal, n, items, L.cvs);
   sd_b3_batch_reduce<<<(uint32_t)std::min<uint64_t>(n, 256 * 4), GROUP, 0, s>>>(
-      gstart, groups, gtotal, n, items, cvs, d_digests);
+      L.gstart, L.groups, L.gtotal, n, items, L.cvs, d_digests);
   return hipGetLastError();
 }
 
-size_t checksum_workspace_bytes(uint64_t len) {
+// the level-wise reduce's two CV lists of g CVs each (reduce_to_one ping-pongs between them)
+CvPingPong cv_pingpong_layout(void* ws, uint64_t g) {
+  WsCarve w(ws);  CvPingPong L;
+  L.a = w.take<uint32_t>(g * 8);  L.b = w.take<uint32_t>(g * 8);
+  w.skip(512);  // reserve nobody reads
+  L.bytes = w.bytes();  return L;
+}
+static uint64_t subtrees_of(uint64_t len) {
   const uint64_t nchunks = len == 0 ? 1 : (len + 1023) >> 10;
-  const uint64_t g = (nchunks + GROUP_CHUNKS - 1) / GROUP_CHUNKS;
-  return 2 * ((g * 32 + 255) / 256 * 256) + 512;
+  return (nchunks + GROUP_CHUNKS - 1) / GROUP_CHUNKS;
+}
+size_t checksum_workspace_bytes(uint64_t len) { return cv_pingpong_layout(nullptr, subtrees_of(len)).bytes; }
+size_t reduce_cvs_workspace_bytes(uint64_t cnt) {
+  return cv_pingpong_layout(nullptr, (cnt + GROUP - 1) / GROUP).bytes;
 }
 
 // Reduce `cnt` CVs at d_cvs (ping-pong with `tmp`) to one; result in *result (device).
@@ -994,14 +999,12 @@ static hipError_t reduce_to_one(uint32_t* a, uint32_t* b, uint64_t cnt, bool roo
 
 hipError_t checksum_device(const uint8_t* data, uint64_t len, uint64_t chunk0, bool root,
                            uint32_t* d_out8, void* ws, hipStream_t s) {
-  const uint64_t nchunks = len == 0 ? 1 : (len + 1023) >> 10;
-  const uint64_t g = (nchunks + GROUP_CHUNKS - 1) / GROUP_CHUNKS;
+  const uint64_t g = subtrees_of(len);
   if (g >= (1ull << 31)) return hipErrorInvalidValue;
-  uint32_t* a = (uint32_t*)ws;
-  uint32_t* b = (uint32_t*)((char*)ws + (g * 32 + 255) / 256 * 256);
-  sd_b3_chunk_groups<<<(uint32_t)g, GROUP, 0, s>>>(data, len, chunk0, a, root ? 1 : 0);
+  const CvPingPong L = cv_pingpong_layout(ws, g);
+  sd_b3_chunk_groups<<<(uint32_t)g, GROUP, 0, s>>>(data, len, chunk0, L.a, root ? 1 : 0);
   uint32_t* res;
-  hipError_t e = reduce_to_one(a, b, g, root, &res, s);
+  hipError_t e = reduce_to_one(L.a, L.b, g, root, &res, s);
   if (e != hipSuccess) return e;
   return hipMemcpyAsync(d_out8, res, 32, hipMemcpyDeviceToDevice, s);
 }
@@ -1010,12 +1013,11 @@ hipError_t reduce_cvs_device(const uint32_t* d_cvs, uint64_t cnt, uint32_t* d_ou
                              hipStream_t s) {
   if (cnt == 0) return hipErrorInvalidValue;
   const uint64_t g = (cnt + GROUP - 1) / GROUP;
-  uint32_t* a = (uint32_t*)ws;
-  uint32_t* b = (uint32_t*)((char*)ws + (g * 32 + 255) / 256 * 256);
+  const CvPingPong L = cv_pingpong_layout(ws, g);
   if (cnt == 1) return hipMemcpyAsync(d_out8, d_cvs, 32, hipMemcpyDeviceToDevice, s);
-  sd_b3_reduce_cvs<<<(uint32_t)g, GROUP, 0, s>>>(d_cvs, cnt, a, 1);
+  sd_b3_reduce_cvs<<<(uint32_t)g, GROUP, 0, s>>>(d_cvs, cnt, L.a, 1);
   uint32_t* res;
-  hipError_t e = reduce_to_one(a, b, g, true, &res, s);
+  hipError_t e = reduce_to_one(L.a, L.b, g, true, &res, s);
   if (e != hipSuccess) return e;
   return hipMemcpyAsync(d_out8, res, 32, hipMemcpyDeviceToDevice, s);
 }

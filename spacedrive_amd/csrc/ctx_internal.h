@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/sd_hip_cas.h"
+#include "sd_ws.h"
 
 struct DevBuf {
   void* p = nullptr;
@@ -294,10 +295,6 @@ inline hipError_t sd_ws_release(sd_cas_ctx* c, hipStream_t s) {
   c->ws_pending = true;
   return hipEventRecord(c->ws_ev, s);
 }
-inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-// packed whole-file contents start on 128-B lines: a K2 lane's line pair is one cache line
-inline size_t up128(size_t x) { return (x + 127) & ~(size_t)127; }
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 // a 32-byte digest as 64 lower-case hex digits and a NUL
 inline void sd_hex32(const uint8_t d[32], char out[65]) {
   static const char* hx = "0123456789abcdef";
@@ -347,6 +344,42 @@ extern "C" hipError_t sd_dispatch_packed(sd_cas_ctx* c, const uint8_t* arena, co
                                          const uint32_t* lens, const uint64_t* sizes, size_t n,
                                          uint64_t* keys, hipStream_t s);
 extern "C" size_t sd_packed_workspace_bytes(const sd_cas_ctx* c, size_t n);
+
+// Workspace layouts of sd_hip_cas.cpp, host_paths.cpp (StagedLayout: byte offsets) and sd_multi.cpp
+// (sd_ws.h; a null base measures).  Internal: exported only so tests/native/ws_layout_test.cpp links them.
+struct PackedWs { uint64_t *lkeys, *skeys; uint32_t* order; void* sort_ws; size_t bytes; };
+struct LinkStagingWs {
+  uint32_t* rep; uint64_t* hkeys; uint32_t *hrows, *minrow; uint64_t* orphans;
+  uint32_t *starts, *counts, *boff; uint64_t* tiles; uint32_t* filter; uint64_t* counters; size_t bytes;
+};
+struct LinkIoWs {
+  uint64_t* keys; uint8_t* state; uint32_t *step, *object; uint8_t* action;
+  uint64_t* seed_keys; uint32_t *seed_objects, *pre; size_t bytes;
+};
+struct StatsWs { uint64_t *shards, *totals; size_t bytes; };
+struct TopWs {
+  uint64_t *hist, *sel; uint32_t* scan; uint64_t* ckeys; uint32_t* cvals; uint64_t* skeys;
+  uint32_t* svals; void* sort_ws; size_t bytes;
+};
+struct DupReportWs {
+  uint64_t *keys, *sizes; uint32_t *rep, *copies; uint8_t* state; uint64_t* hkeys;
+  uint32_t *hrows, *minrow; uint64_t* orphans; uint32_t* top_heads; uint64_t *top_waste, *counters; size_t bytes;
+};
+struct StagedLayout { size_t packed, sizes, poffs, plens, keys, h2d_bytes, bytes; };
+struct MultiBufs {
+  uint64_t* skeys; uint32_t* sidx; uint64_t* gidx; uint64_t* splits; uint64_t* back;
+  uint64_t* rkeys; uint64_t* ridx; uint64_t* k2; uint32_t* pos; uint32_t* rep_pos; uint64_t* repg; size_t bytes;
+};
+MultiBufs sd_multi_bufs_layout(void* base, size_t n, size_t m, int G);
+extern "C" {
+StagedLayout sd_staged_layout(size_t sampled_bytes, size_t packed_bytes, size_t ns, size_t np, size_t n);
+PackedWs sd_packed_layout(void* ws, size_t n);
+LinkStagingWs sd_link_staging_layout(void* base, size_t n, size_t n_seed, size_t steps_total, bool pre);
+LinkIoWs sd_link_io_layout(void* base, size_t n, size_t n_seed, bool pre);
+StatsWs sd_stats_layout(void* ws);
+TopWs sd_top_layout(void* ws, uint64_t n, uint64_t m);
+DupReportWs sd_dup_report_layout(void* base, size_t n, bool state, size_t k);
+}
 
 inline int sd_ensure_pinned(sd_cas_ctx* c, size_t bytes) {
   if (bytes <= c->pinned_bytes) return SD_CAS_OK;

@@ -18,6 +18,7 @@
 
 #include "sd_debug.h"
 #include "sd_group.h"
+#include "sd_ws.h"
 
 namespace sdcas {
 
@@ -535,21 +536,28 @@ namespace sdcas {
 
 SD_DBG_ACCESSOR(sd_dbg_violations_group)
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline uint32_t tiles_of(uint64_t n, uint64_t tile) { return (uint32_t)((n + tile - 1) / tile); }
 
-size_t sort_workspace_bytes(uint64_t n) {
-  const uint64_t nt = tiles_of(n ? n : 1, TILE);
-  const uint64_t nb = tiles_of(nt, UP_TILES);
-  return align_up(n * 8, 256) + align_up(n * 4, 256) + align_up(RADIX * nt * 4, 256) +
-         align_up(RADIX * nb * 4, 256) + align_up(RADIX * 4, 256) + 256;
+SortWs sort_layout(void* ws, uint64_t n) {
+  const uint64_t nt = tiles_of(n ? n : 1, TILE), nb = tiles_of(nt, UP_TILES);
+  WsCarve w(ws);  SortWs L;
+  L.kalt = w.take<uint64_t>(n);  L.valt = w.take<uint32_t>(n);
+  L.hist = w.take<uint32_t>(RADIX * nt);  L.bsum = w.take<uint32_t>(RADIX * nb);
+  L.rowtot = w.take<uint32_t>(RADIX);
+  w.skip(256);  // reserve nobody reads
+  L.bytes = w.bytes();  return L;
 }
+size_t sort_workspace_bytes(uint64_t n) { return sort_layout(nullptr, n).bytes; }
 
-size_t group_workspace_bytes(uint64_t n) {
+GroupWs group_layout(void* ws, uint64_t n) {
   const uint64_t ng = tiles_of(n ? n : 1, SCAN_TILE);
-  return sort_workspace_bytes(n) + align_up(n * 8, 256) + align_up(n * 4, 256) +
-         3 * align_up(ng * 4, 256) + 256;
+  WsCarve w(ws);  GroupWs L;
+  L.sort_ws = w.nest(sort_workspace_bytes(n));
+  L.skeys = w.take<uint64_t>(n);  L.svals = w.take<uint32_t>(n);  L.heads = w.take<uint32_t>(ng);
+  w.skip(2 * up256(ng * 4) + 256);  // two more ng-word arrays and 256 B nobody reads
+  L.bytes = w.bytes();  return L;
 }
+size_t group_workspace_bytes(uint64_t n) { return group_layout(nullptr, n).bytes; }
 
 hipError_t exclusive_scan_u32(const uint32_t* in, uint32_t* out, uint64_t m, uint32_t* partial,
                               hipStream_t s, unsigned long long* total) {
@@ -576,12 +584,7 @@ hipError_t radix_sort_pairs(const uint64_t* keys_in, const uint32_t* vals_in, ui
     return hipErrorInvalidValue;
   const uint32_t nt = tiles_of(n, TILE);
   const uint32_t nb = tiles_of(nt, UP_TILES);
-  char* p = (char*)ws;
-  uint64_t* kalt = (uint64_t*)p; p += align_up(n * 8, 256);
-  uint32_t* valt = (uint32_t*)p; p += align_up(n * 4, 256);
-  uint32_t* hist = (uint32_t*)p; p += align_up((uint64_t)RADIX * nt * 4, 256);
-  uint32_t* bsum = (uint32_t*)p; p += align_up((uint64_t)RADIX * nb * 4, 256);
-  uint32_t* rowtot = (uint32_t*)p;
+  const SortWs L = sort_layout(ws, n);
   const int passes = (end_bit - begin_bit + 7) / 8;
   const uint64_t* ksrc = keys_in;
   const uint32_t* vsrc = vals_in;
@@ -590,16 +593,16 @@ hipError_t radix_sort_pairs(const uint64_t* keys_in, const uint32_t* vals_in, ui
     const int bits = (end_bit - (int)shift) < 8 ? (end_bit - (int)shift) : 8;
     const uint32_t mask = (1u << bits) - 1u;
     const bool to_out = ((passes - 1 - i) % 2) == 0;
-    uint64_t* kdst = to_out ? keys_out : kalt;
-    uint32_t* vdst = to_out ? vals_out : valt;
-    sd_radix_upsweep<<<nb, UP_THREADS, 0, s>>>(ksrc, n, shift, mask, hist, bsum, nt);
-    sd_radix_blockscan<<<RADIX / BSCAN_DIGITS, BSCAN_DIGITS * BSCAN_SEGS, 0, s>>>(bsum, nb, rowtot);
+    uint64_t* kdst = to_out ? keys_out : L.kalt;
+    uint32_t* vdst = to_out ? vals_out : L.valt;
+    sd_radix_upsweep<<<nb, UP_THREADS, 0, s>>>(ksrc, n, shift, mask, L.hist, L.bsum, nt);
+    sd_radix_blockscan<<<RADIX / BSCAN_DIGITS, BSCAN_DIGITS * BSCAN_SEGS, 0, s>>>(L.bsum, nb, L.rowtot);
     if (vsrc)
-      sd_radix_scatter<<<nt, SORT_THREADS, 0, s>>>(ksrc, vsrc, kdst, vdst, n, shift, mask, hist, bsum,
-                                                   rowtot, nt);
+      sd_radix_scatter<<<nt, SORT_THREADS, 0, s>>>(ksrc, vsrc, kdst, vdst, n, shift, mask, L.hist, L.bsum,
+                                                   L.rowtot, nt);
     else
-      sd_radix_scatter_iota<<<nt, SORT_THREADS, 0, s>>>(ksrc, kdst, vdst, n, shift, mask, hist, bsum,
-                                                        rowtot, nt, iota_out);
+      sd_radix_scatter_iota<<<nt, SORT_THREADS, 0, s>>>(ksrc, kdst, vdst, n, shift, mask, L.hist, L.bsum,
+                                                        L.rowtot, nt, iota_out);
     ksrc = kdst;
     vsrc = vdst;
   }
@@ -622,19 +625,23 @@ hipError_t group_sorted(const uint64_t* skeys, const uint32_t* svals, uint64_t n
 hipError_t group_keys(const uint64_t* keys, uint64_t n, uint32_t* rep, uint64_t* d_objects,
                       void* ws, hipStream_t s) {
   if (n == 0) return hipMemsetAsync(d_objects, 0, 8, s);
-  char* p = (char*)ws;
-  char* sort_ws = p; p += sort_workspace_bytes(n);
-  uint64_t* skeys = (uint64_t*)p; p += align_up(n * 8, 256);
-  uint32_t* svals = (uint32_t*)p; p += align_up(n * 4, 256);
+  const GroupWs L = group_layout(ws, n);
   // (the first pass also writes rep[i] = i: the runs kernel then stores only duplicates)
-  hipError_t e = radix_sort_pairs(keys, nullptr, skeys, svals, n, 0, 64, sort_ws, s, rep);
+  hipError_t e = radix_sort_pairs(keys, nullptr, L.skeys, L.svals, n, 0, 64, L.sort_ws, s, rep);
   if (e != hipSuccess) return e;
-  return group_sorted(skeys, svals, n, rep, d_objects, p, s, true);
+  return group_sorted(L.skeys, L.svals, n, rep, d_objects, L.heads, s, true);
 }
 
-size_t group_min_sorted_workspace_bytes(uint64_t n) {
-  return group_workspace_bytes(n) + 3 * align_up(n * 8, 256) + 3 * align_up(n * 4, 256) + 256;
+GroupMinSortedWs group_min_sorted_layout(void* ws, uint64_t n) {
+  WsCarve w(ws);  GroupMinSortedWs L;
+  L.gws = w.nest(group_workspace_bytes(n));
+  L.vkey = w.take<uint64_t>(n);  L.k2 = w.take<uint64_t>(n);
+  L.skeys = w.take<uint64_t>(n);  L.order = w.take<uint32_t>(n);
+  L.spos = w.take<uint32_t>(n);  L.rep = w.take<uint32_t>(n);
+  w.skip(256);  // reserve nobody reads
+  L.bytes = w.bytes();  return L;
 }
+size_t group_min_sorted_workspace_bytes(uint64_t n) { return group_min_sorted_layout(nullptr, n).bytes; }
 
 // out[i] = min{ val(j) : keys[j] == keys[i] } through two stable LSD sorts: positions by
 // value (32 bits), then by key (64 bits) — inside every equal-key run the positions ascend
@@ -643,25 +650,19 @@ size_t group_min_sorted_workspace_bytes(uint64_t n) {
 hipError_t group_min_by_sort(const uint64_t* keys, const uint32_t* vals, uint64_t n, uint32_t* out,
                              uint64_t* d_objects, void* ws, hipStream_t s) {
   if (n == 0) return hipMemsetAsync(d_objects, 0, 8, s);
-  char* p = (char*)ws;
-  char* gws = p; p += group_workspace_bytes(n);
-  uint64_t* vkey = (uint64_t*)p; p += align_up(n * 8, 256);
-  uint64_t* k2 = (uint64_t*)p; p += align_up(n * 8, 256);
-  uint64_t* skeys = (uint64_t*)p; p += align_up(n * 8, 256);
-  uint32_t* order = (uint32_t*)p; p += align_up(n * 4, 256);
-  uint32_t* spos = (uint32_t*)p; p += align_up(n * 4, 256);
-  uint32_t* rep = (uint32_t*)p;
+  const GroupMinSortedWs L = group_min_sorted_layout(ws, n);
   const uint32_t nb = tiles_of(n, 256);
-  sd_widen_vals<<<nb, 256, 0, s>>>(vals, n, vkey);
+  sd_widen_vals<<<nb, 256, 0, s>>>(vals, n, L.vkey);
   // (spos is a permutation of the positions, so rep can be prefilled by the first sort)
-  hipError_t e = radix_sort_pairs(vkey, nullptr, k2, order, n, 0, 32, gws, s, rep);
+  hipError_t e = radix_sort_pairs(L.vkey, nullptr, L.k2, L.order, n, 0, 32, L.gws, s, L.rep);
   if (e != hipSuccess) return e;
-  sd_gather_keys<<<nb, 256, 0, s>>>(keys, order, n, k2);
-  e = radix_sort_pairs(k2, order, skeys, spos, n, 0, 64, gws, s);
+  sd_gather_keys<<<nb, 256, 0, s>>>(keys, L.order, n, L.k2);
+  e = radix_sort_pairs(L.k2, L.order, L.skeys, L.spos, n, 0, 64, L.gws, s);
   if (e != hipSuccess) return e;
-  e = group_sorted(skeys, spos, n, rep, d_objects, gws, s, true);
+  // intended aliasing: the run-head counts go to the start of L.gws, the sort workspace, dead by now
+  e = group_sorted(L.skeys, L.spos, n, L.rep, d_objects, L.gws, s, true);
   if (e != hipSuccess) return e;
-  sd_gather_vals<<<nb, 256, 0, s>>>(vals, rep, n, out);
+  sd_gather_vals<<<nb, 256, 0, s>>>(vals, L.rep, n, out);
   return hipGetLastError();
 }
 

@@ -42,6 +42,7 @@
 #include "sd_debug.h"
 #include "sd_group.h"
 #include "sd_mix.h"
+#include "sd_ws.h"
 
 namespace sdcas {
 
@@ -1248,39 +1249,30 @@ sd_part_refine_regions(const uint64_t* __restrict__ rkeys, const uint32_t* __res
 // ---- host launchers ----------------------------------------------------------------
 namespace sdcas {
 
-static inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-
-// Fixed region capacity of the fused chain for a batch of n uniform keys: the mean coarse
-// bucket + 8 standard deviations (binomial) + 64 rows (the exchange's fixed_capacity rule).
-uint64_t region_capacity(uint64_t n) {
-  const double mean = (double)n / REGIONS;
-  const double var = mean * (1.0 - 1.0 / REGIONS);
+// Fixed region capacity for a batch of n uniform keys in nb coarse buckets: the mean bucket +
+// 8 standard deviations (binomial) + 64 rows (the exchange's fixed_capacity rule).
+static uint64_t region_capacity_nb(uint64_t n, uint32_t nb) {
+  const double mean = (double)n / nb;
+  const double var = mean * (1.0 - 1.0 / nb);
   uint64_t sd = 1;
   while ((double)(sd * sd) < var) ++sd;
   return (uint64_t)mean + 1 + 8 * sd + 64;
 }
+uint64_t region_capacity(uint64_t n) { return region_capacity_nb(n, REGIONS); }  // the fused chain's
 
 bool region_group_supported(uint64_t n) { return n > 0 && n <= BIG_MAX_KEYS; }
 
 // workspace: rkeys | rfile | global overflow tables (2 slots per region row) | spill list
-// (keys, files: n rows at most)
-size_t region_group_workspace_bytes(uint64_t n) {
+// (keys, files: n rows at most) | objects u64, overflow carve cursor u64
+RegionGroupWs region_group_layout(void* ws, uint64_t n) {
   const uint64_t rows = (uint64_t)REGIONS * region_capacity(n);
-  return al256(rows * 8) + al256(rows * 4) + al256(2 * rows * 8) + al256(2 * rows * 4) +
-         al256(n * 8) + al256(n * 4);
+  WsCarve w(ws);  RegionGroupWs L;
+  L.rkeys = w.take<uint64_t>(rows);  L.rfile = w.take<uint32_t>(rows);
+  L.gkeys = w.take<uint64_t>(2 * rows);  L.gvals = w.take<uint32_t>(2 * rows);
+  L.spill_keys = w.take<uint64_t>(n);  L.spill_file = w.take<uint32_t>(n);  L.objects = w.take<uint64_t>(2);
+  L.bytes = w.bytes();  return L;
 }
-
-void region_group_layout(void* ws, uint64_t n, uint64_t** rkeys, uint32_t** rfile, uint64_t** gkeys,
-                         uint32_t** gvals, uint64_t** spill_keys, uint32_t** spill_file) {
-  const uint64_t rows = (uint64_t)REGIONS * region_capacity(n);
-  char* q = (char*)ws;
-  *rkeys = (uint64_t*)q; q += al256(rows * 8);
-  *rfile = (uint32_t*)q; q += al256(rows * 4);
-  *gkeys = (uint64_t*)q; q += al256(2 * rows * 8);
-  *gvals = (uint32_t*)q; q += al256(2 * rows * 4);
-  *spill_keys = (uint64_t*)q; q += al256(n * 8);
-  *spill_file = (uint32_t*)q;
-}
+size_t region_group_workspace_bytes(uint64_t n) { return region_group_layout(nullptr, n).bytes; }
 
 hipError_t region_group_min(const uint64_t* rkeys, const uint32_t* rfile, uint32_t* cursor,
                             uint64_t cap, uint32_t* out, uint64_t* d_objects, uint64_t* gkeys,
@@ -1368,19 +1360,15 @@ static bool small_regions(uint64_t n, uint64_t target) {
 #ifndef SD_BIG_REGIONS
 #define SD_BIG_REGIONS 1
 #endif
-static uint64_t region_capacity_nb(uint64_t n, uint32_t nb) {
-  const double mean = (double)n / nb;
-  const double var = mean * (1.0 - 1.0 / nb);
-  uint64_t sd = 1;
-  while ((double)(sd * sd) < var) ++sd;
-  return (uint64_t)mean + 1 + 8 * sd + 64;
-}
 
 // its workspace: rkeys | rfile | overflow tables (2n slots) | carve cursor | spill list (n rows)
-static size_t small_regions_bytes(uint64_t n) {
+SmallRegionsWs small_regions_layout(void* ws, uint64_t n) {
   const uint64_t rows = (uint64_t)REGIONS * region_capacity(n);
-  return al256(rows * 8) + al256(rows * 4) + al256(2 * n * 8) + al256(2 * n * 4) + 256 +
-         al256(n * 8) + al256(n * 4);
+  WsCarve w(ws);  SmallRegionsWs L;
+  L.rkeys = w.take<uint64_t>(rows);  L.rfile = w.take<uint32_t>(rows);
+  L.gkeys = w.take<uint64_t>(2 * n);  L.gvals = w.take<uint32_t>(2 * n);
+  L.spill = w.take<unsigned long long>(1);  L.skeys = w.take<uint64_t>(n);  L.sfile = w.take<uint32_t>(n);
+  L.bytes = w.bytes();  return L;
 }
 
 static bool big_regions(const GroupPlan& g, uint64_t target) {
@@ -1388,32 +1376,49 @@ static bool big_regions(const GroupPlan& g, uint64_t target) {
 }
 
 // rkeys | rfile | spill keys | spill rows | k2 | p2 | starts | Object-count shards | overflow
-// tables (2n slots)
-static size_t big_regions_bytes(uint64_t n, const GroupPlan& g) {
+// tables (2n slots).  The default-target plan's layout: big_regions() admits target == 0 only.
+BigRegionsWs big_regions_layout(void* ws, uint64_t n) {
+  const GroupPlan g = group_plan(n, 0);  // (= hash_group_min's plan whenever it takes this chain)
   const uint64_t rows = (uint64_t)g.l1.nb * region_capacity_nb(n, g.l1.nb);
-  return al256(rows * 8) + al256(rows * 4) + 2 * (al256(n * 8) + al256(n * 4)) +
-         al256((size_t)g.nb() * 4) + al256(OBJ_SHARDS * OBJ_STRIDE * 8) + al256(2 * n * 8) +
-         al256(2 * n * 4);
+  WsCarve w(ws);  BigRegionsWs L;
+  L.rkeys = w.take<uint64_t>(rows);  L.rfile = w.take<uint32_t>(rows);
+  L.skeys = w.take<uint64_t>(n);  L.spos = w.take<uint32_t>(n);
+  L.k2 = w.take<uint64_t>(n);  L.p2 = w.take<uint32_t>(n);
+  L.starts = w.take<uint32_t>(g.nb());  L.shards = w.take<unsigned long long>(OBJ_SHARDS * OBJ_STRIDE);
+  L.gkeys = w.take<uint64_t>(2 * n);  L.gvals = w.take<uint32_t>(2 * n);
+  L.bytes = w.bytes();  return L;
 }
 
-// workspace: k1 | p1 | k2 | p2 | fill (repl copies) | starts1 | starts | Object-count shards |
-// overflow tables (the bucket totals live in a persistent buffer of the caller,
+// the two-level chain: k1 | p1 | k2 | p2 | fill (repl copies) | starts1 | starts | Object-count
+// shards | overflow tables (the bucket totals live in a persistent buffer of the caller,
 // GROUP_TOTALS_WORDS)
-size_t hash_group_workspace_bytes(uint64_t n, uint64_t target) {
+HashChainWs hash_chain_layout(void* ws, uint64_t n, uint64_t target) {
   const GroupPlan g = group_plan(n, target);
-  const size_t nb1 = g.l1.nb;
-  const size_t chain = 2 * (al256(n * 8) + al256(n * 4)) + al256(totals_repl(nb1) * nb1 * 4) +
-                       al256(nb1 * 4) + al256((size_t)g.nb() * 4) +
-                       al256(OBJ_SHARDS * OBJ_STRIDE * 8) + al256(2 * n * 8) + al256(2 * n * 4);
-  if (small_regions(n, target)) return std::max(chain, small_regions_bytes(n));
-  if (big_regions(g, target)) return std::max(chain, big_regions_bytes(n, g));
+  const uint64_t nb1 = g.l1.nb;
+  WsCarve w(ws);  HashChainWs L;
+  L.k1 = w.take<uint64_t>(n);  L.p1 = w.take<uint32_t>(n);
+  L.k2 = w.take<uint64_t>(n);  L.p2 = w.take<uint32_t>(n);
+  L.fill = w.take<uint32_t>(totals_repl((uint32_t)nb1) * nb1);  L.starts1 = w.take<uint32_t>(nb1);
+  L.starts = w.take<uint32_t>(g.nb());  L.shards = w.take<unsigned long long>(OBJ_SHARDS * OBJ_STRIDE);
+  L.gkeys = w.take<uint64_t>(2 * n);  L.gvals = w.take<uint32_t>(2 * n);
+  L.bytes = w.bytes();  return L;
+}
+// (ws serves whichever chain hash_group_min picks)
+size_t hash_group_workspace_bytes(uint64_t n, uint64_t target) {
+  const size_t chain = hash_chain_layout(nullptr, n, target).bytes;
+  if (small_regions(n, target)) return std::max(chain, small_regions_layout(nullptr, n).bytes);
+  if (big_regions(group_plan(n, target), target)) return std::max(chain, big_regions_layout(nullptr, n).bytes);
   return chain;
 }
 
-size_t partition_workspace_bytes(uint64_t n, uint32_t parts) {
-  (void)n;
-  return 2 * al256((size_t)totals_repl(parts) * parts * 4);
+// totals | fill (repl copies each)
+PartitionWs partition_layout(void* ws, uint32_t parts) {
+  WsCarve w(ws);  PartitionWs L;
+  L.totals = w.take<uint32_t>((uint64_t)totals_repl(parts) * parts);
+  L.fill = w.take<uint32_t>((uint64_t)totals_repl(parts) * parts);
+  L.bytes = w.bytes();  return L;
 }
+size_t partition_workspace_bytes(uint64_t, uint32_t parts) { return partition_layout(nullptr, parts).bytes; }
 
 // the Object count of a sharded chain: *objects = the sum of its shards
 extern "C" __global__ void __launch_bounds__(64)
@@ -1497,21 +1502,13 @@ hipError_t hash_group_min(const uint64_t* keys, const uint32_t* vals, uint64_t n
   static_assert((1024 + 1) * CURSOR_STRIDE <= GROUP_TOTALS_WORDS,
                 "the big chain's cursors and spill count fit the totals buffer");
   if (small_regions(n, target)) {  // `totals` (zero, left zero) holds the region cursors
-    const uint64_t cap = region_capacity(n), rows = (uint64_t)REGIONS * cap;
-    char* q = (char*)ws;
-    uint64_t* rkeys = (uint64_t*)q; q += al256(rows * 8);
-    uint32_t* rfile = (uint32_t*)q; q += al256(rows * 4);
-    uint64_t* gkeys = (uint64_t*)q; q += al256(2 * n * 8);
-    uint32_t* gvals = (uint32_t*)q; q += al256(2 * n * 4);
-    unsigned long long* spill = (unsigned long long*)q; q += 256;
-    uint64_t* skeys = (uint64_t*)q; q += al256(n * 8);
-    uint32_t* sfile = (uint32_t*)q;
+    const uint64_t cap = region_capacity(n);
+    const SmallRegionsWs L = small_regions_layout(ws, n);
     unsigned long long* obj = (unsigned long long*)d_objects;
     sd_region_partition<<<(uint32_t)((n + RPART_TILE - 1) / RPART_TILE), RPART_THREADS, 0, s>>>(
-        keys, vals, n, rkeys, rfile, totals, cap, out, obj, spill, skeys, sfile);
-    sd_bucket_min_regions_keys<<<REGIONS, REG_THREADS, 0, s>>>(rkeys, rfile, totals, cap, keys, vals,
-                                                               n, out, obj, gkeys, gvals, spill, skeys,
-                                                               sfile);
+        keys, vals, n, L.rkeys, L.rfile, totals, cap, out, obj, L.spill, L.skeys, L.sfile);
+    sd_bucket_min_regions_keys<<<REGIONS, REG_THREADS, 0, s>>>(
+        L.rkeys, L.rfile, totals, cap, keys, vals, n, out, obj, L.gkeys, L.gvals, L.spill, L.skeys, L.sfile);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) (void)hipMemsetAsync(totals, 0, GROUP_TOTALS_WORDS * 4, s);  // restore
     return e;
@@ -1519,18 +1516,8 @@ hipError_t hash_group_min(const uint64_t* keys, const uint32_t* vals, uint64_t n
   const GroupPlan g = group_plan(n, target);
   const size_t nb1 = g.l1.nb;
   if (big_regions(g, target)) {  // `totals` (zero, left zero) holds the cursors + spill count
-    const uint64_t cap = region_capacity_nb(n, (uint32_t)nb1), rows = nb1 * cap;
-    char* q = (char*)ws;
-    uint64_t* rkeys = (uint64_t*)q; q += al256(rows * 8);
-    uint32_t* rfile = (uint32_t*)q; q += al256(rows * 4);
-    uint64_t* skeys = (uint64_t*)q; q += al256(n * 8);
-    uint32_t* spos = (uint32_t*)q; q += al256(n * 4);
-    uint64_t* k2 = (uint64_t*)q; q += al256(n * 8);
-    uint32_t* p2 = (uint32_t*)q; q += al256(n * 4);
-    uint32_t* starts = (uint32_t*)q; q += al256((size_t)g.nb() * 4);
-    unsigned long long* shards = (unsigned long long*)q; q += al256(OBJ_SHARDS * OBJ_STRIDE * 8);
-    uint64_t* gkeys = (uint64_t*)q; q += al256(2 * n * 8);
-    uint32_t* gvals = (uint32_t*)q;
+    const uint64_t cap = region_capacity_nb(n, (uint32_t)nb1);
+    const BigRegionsWs L = big_regions_layout(ws, n);
     uint32_t* spill_cnt = totals + nb1 * CURSOR_STRIDE;
     const uint32_t twords = (uint32_t)(nb1 * CURSOR_STRIDE + CURSOR_STRIDE);
     const uint64_t tiles = (n + RBIG_TILE - 1) / RBIG_TILE;
@@ -1538,53 +1525,43 @@ hipError_t hash_group_min(const uint64_t* keys, const uint32_t* vals, uint64_t n
     // tile and 16,384-key tiles staged in two passes no faster: profiles/r03b_group_ab/README.md
     // "big"; the two-pass variant was removed in round 4)
     sd_region_partition_big<<<(uint32_t)tiles, RBIG_THREADS, 0, s>>>(
-        keys, vals, n, g.b1, rkeys, rfile, totals, cap, out, shards, OBJ_SHARDS, spill_cnt, skeys, spos);
-    sd_part_refine_regions<<<(uint32_t)nb1, PART_THREADS, 0, s>>>(rkeys, rfile, totals, cap, g.b1, g.b2,
-                                                                  spill_cnt, skeys, spos, k2, p2, starts);
-    sd_bucket_min<<<g.nb(), MIN_THREADS, 0, s>>>(k2, p2, vals, starts, g.nb(), g.b1 + g.b2, n, out,
-                                                 shards, gkeys, gvals, totals, twords);
-    sd_objects_sum<<<1, 64, 0, s>>>(shards, OBJ_SHARDS, (unsigned long long*)d_objects);
+        keys, vals, n, g.b1, L.rkeys, L.rfile, totals, cap, out, L.shards, OBJ_SHARDS, spill_cnt, L.skeys, L.spos);
+    sd_part_refine_regions<<<(uint32_t)nb1, PART_THREADS, 0, s>>>(
+        L.rkeys, L.rfile, totals, cap, g.b1, g.b2, spill_cnt, L.skeys, L.spos, L.k2, L.p2, L.starts);
+    sd_bucket_min<<<g.nb(), MIN_THREADS, 0, s>>>(L.k2, L.p2, vals, L.starts, g.nb(), g.b1 + g.b2, n, out,
+                                                 L.shards, L.gkeys, L.gvals, totals, twords);
+    sd_objects_sum<<<1, 64, 0, s>>>(L.shards, OBJ_SHARDS, (unsigned long long*)d_objects);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) (void)hipMemsetAsync(totals, 0, GROUP_TOTALS_WORDS * 4, s);  // restore
     return e;
   }
-  char* q = (char*)ws;
-  uint64_t* k1 = (uint64_t*)q; q += al256(n * 8);
-  uint32_t* p1 = (uint32_t*)q; q += al256(n * 4);
-  uint64_t* k2 = (uint64_t*)q; q += al256(n * 8);
-  uint32_t* p2 = (uint32_t*)q; q += al256(n * 4);
-  uint32_t* fill = (uint32_t*)q; q += al256(totals_repl(nb1) * nb1 * 4);
-  uint32_t* starts1 = (uint32_t*)q; q += al256(nb1 * 4);
-  uint32_t* starts = (uint32_t*)q; q += al256((size_t)g.nb() * 4);
-  unsigned long long* shards = (unsigned long long*)q; q += al256(OBJ_SHARDS * OBJ_STRIDE * 8);
-  uint64_t* gkeys = (uint64_t*)q; q += al256(2 * n * 8);
-  uint32_t* gvals = (uint32_t*)q;
+  const HashChainWs L = hash_chain_layout(ws, n, target);
   const uint32_t twords = totals_repl((uint32_t)nb1) * (uint32_t)nb1;  // <= GROUP_TOTALS_WORDS
   // the fine-bucket tables count into the shards (summed after them); the big tables (<= 256
   // workgroups) straight into d_objects
   const bool sharded = !g.big && OBJ_SHARDS > 1;
-  unsigned long long* objects = sharded ? shards : (unsigned long long*)d_objects;
-  hipError_t e = run_partition(keys, n, g.l1, 0, k1, p1, totals, true, fill, starts1, nullptr,
+  unsigned long long* objects = sharded ? L.shards : (unsigned long long*)d_objects;
+  hipError_t e = run_partition(keys, n, g.l1, 0, L.k1, L.p1, totals, true, L.fill, L.starts1, nullptr,
                                objects, sharded ? OBJ_SHARDS : 1, s, vals, out);
   if (e != hipSuccess) {
     (void)hipMemsetAsync(totals, 0, GROUP_TOTALS_WORDS * 4, s);  // restore the invariant
     return e;
   }
-  const uint64_t* fk = k1;
-  const uint32_t* fp = p1;
-  const uint32_t* fstarts = starts1;
+  const uint64_t* fk = L.k1;
+  const uint32_t* fp = L.p1;
+  const uint32_t* fstarts = L.starts1;
   if (g.b2 > 0) {
-    sd_part_refine<<<(uint32_t)nb1, PART_THREADS, 0, s>>>(k1, p1, starts1, (uint32_t)nb1, n, g.b1,
-                                                          g.b2, k2, p2, starts);
-    fk = k2;
-    fp = p2;
-    fstarts = starts;
+    sd_part_refine<<<(uint32_t)nb1, PART_THREADS, 0, s>>>(L.k1, L.p1, L.starts1, (uint32_t)nb1, n, g.b1,
+                                                          g.b2, L.k2, L.p2, L.starts);
+    fk = L.k2;
+    fp = L.p2;
+    fstarts = L.starts;
   }
   // (above 1.44M keys, refining into these big tables instead — 4,096 buckets of ~3,050 at
   // 12.5M — was 1.13x slower: profiles/r02b_group_big_tables_ab.log)
   if (g.big)
     sd_bucket_min_big<<<g.nb(), BIG_THREADS, 0, s>>>(fk, fp, vals, fstarts, g.nb(), g.b1, n, out,
-                                                     (unsigned long long*)d_objects, gkeys, gvals,
+                                                     (unsigned long long*)d_objects, L.gkeys, L.gvals,
                                                      totals, twords);
   else
     // one workgroup per fine bucket: a persistent grid walking the buckets (with or without
@@ -1594,8 +1571,8 @@ hipError_t hash_group_min(const uint64_t* keys, const uint32_t* vals, uint64_t n
     // profiles/r02b_group_small_tables_ab.log)
   {
     sd_bucket_min<<<g.nb(), MIN_THREADS, 0, s>>>(fk, fp, vals, fstarts, g.nb(), g.b1 + g.b2, n, out,
-                                                 objects, gkeys, gvals, totals, twords);
-    if (sharded) sd_objects_sum<<<1, 64, 0, s>>>(shards, OBJ_SHARDS, (unsigned long long*)d_objects);
+                                                 objects, L.gkeys, L.gvals, totals, twords);
+    if (sharded) sd_objects_sum<<<1, 64, 0, s>>>(L.shards, OBJ_SHARDS, (unsigned long long*)d_objects);
   }
   e = hipGetLastError();
   if (e != hipSuccess) (void)hipMemsetAsync(totals, 0, GROUP_TOTALS_WORDS * 4, s);  // restore
@@ -1607,9 +1584,8 @@ hipError_t partition_range(const uint64_t* keys, uint64_t n, uint32_t parts, uin
   if (parts == 0 || parts > MAX_BUCKETS || n >= (1ull << 32)) return hipErrorInvalidValue;
   if (n == 0) return hipMemsetAsync(d_counts, 0, (size_t)parts * 8, s);
   const PartPlan p = part_plan(n, parts);
-  uint32_t* totals = (uint32_t*)ws;
-  uint32_t* fill = (uint32_t*)((char*)ws + al256((size_t)totals_repl(parts) * parts * 4));
-  return run_partition(keys, n, p, 1, out_keys, out_pos, totals, false, fill, nullptr, d_counts,
+  const PartitionWs L = partition_layout(ws, parts);
+  return run_partition(keys, n, p, 1, out_keys, out_pos, L.totals, false, L.fill, nullptr, d_counts,
                        nullptr, 0, s);
 }
 

@@ -75,13 +75,29 @@ static int plan_batch(sd_cas_ctx* c, const uint64_t* buf_lens, const uint64_t* s
   return SD_CAS_OK;
 }
 
+// Byte offsets of a staged batch of n files (ns sampled, np whole), the same in pinned memory and
+// on the device: sampled content (at 0) | packed content | sizes (the content's end) | poffs |
+// plens | keys.  Everything before the keys crosses the host link (h2d_bytes).
+StagedLayout sd_staged_layout(size_t sampled_bytes, size_t packed_bytes, size_t ns, size_t np, size_t n) {
+  WsCarve w(nullptr);  StagedLayout L;
+  w.skip(sampled_bytes);
+  L.packed = w.bytes(); w.take<uint8_t>(packed_bytes);
+  L.sizes = w.bytes(); w.take<uint64_t>(ns + np);
+  L.poffs = w.bytes(); w.take<uint64_t>(np);
+  L.plens = w.bytes(); w.take<uint32_t>(np);
+  L.keys = L.h2d_bytes = w.bytes(); w.take<uint64_t>(n);
+  L.bytes = w.bytes();  return L;
+}
+static StagedLayout staged_layout(const Plan& pl, size_t n) {
+  return sd_staged_layout(pl.sampled_bytes, pl.packed_bytes, pl.sampled.size(), pl.packed.size(), n);
+}
+
 // Host side of a staged batch's metadata (sizes of both sub-batches, packed offsets; the
-// packed lens are written by the caller): [content][sizes][poffs][plens][keys].
-static void stage_meta(const Plan& pl, const uint64_t* sizes, char* pin) {
+// packed lens are written by the caller)
+static void stage_meta(const Plan& pl, const StagedLayout& L, const uint64_t* sizes, char* pin) {
   const size_t ns = pl.sampled.size(), np = pl.packed.size();
-  const size_t content_bytes = pl.sampled_bytes + up256(pl.packed_bytes);
-  uint64_t* h_sizes = (uint64_t*)(pin + content_bytes);
-  uint64_t* h_poffs = (uint64_t*)((char*)h_sizes + up256((ns + np) * 8));
+  uint64_t* h_sizes = (uint64_t*)(pin + L.sizes);
+  uint64_t* h_poffs = (uint64_t*)(pin + L.poffs);
   for (size_t k = 0; k < ns; k++) h_sizes[k] = sizes[pl.sampled[k]];
   for (size_t k = 0; k < np; k++) h_sizes[ns + k] = sizes[pl.packed[k]];
   for (size_t k = 0; k < np; k++) h_poffs[k] = pl.poff[k];
@@ -94,104 +110,69 @@ static void stage_meta(const Plan& pl, const uint64_t* sizes, char* pin) {
 #define SD_PATHS_KEYS_TO_HOST 1
 #endif
 
-// byte offset of the keys in a staged batch: content | sizes | poffs | plens | keys
-static size_t staged_keys_offset(const Plan& pl) {
-  const size_t ns = pl.sampled.size(), np = pl.packed.size();
-  return pl.sampled_bytes + up256(pl.packed_bytes) + up256((ns + np) * 8) + up256(np * 8) + up256(np * 4);
-}
-
 // Enqueues, for a batch staged in pinned memory at `pin` (stage_meta done): H2D of
 // [h2d_lo, h2d_hi) of the staging to `dev` on the copy stream (the rest is already there),
 // both hash sub-batches on the compute stream after it, their keys into `pin`'s keys area
 // (scatter_keys reads them there).  `done` (optional) is recorded on the compute stream after it.
-// The device-side views of a staged batch: content | sizes | poffs | plens, keys in `pin`
-// (SD_PATHS_KEYS_TO_HOST) or on the device.
-struct StagedDev {
-  uint64_t* sizes;
-  uint64_t* poffs;
-  uint32_t* plens;
-  uint64_t* keys;
-};
-static StagedDev staged_dev(const Plan& pl, char* pin, char* dev) {
-  const size_t ns = pl.sampled.size(), np = pl.packed.size();
-  const size_t content_bytes = pl.sampled_bytes + up256(pl.packed_bytes);
-  StagedDev d;
-  d.sizes = (uint64_t*)(dev + content_bytes);
-  d.poffs = (uint64_t*)((char*)d.sizes + up256((ns + np) * 8));
-  d.plens = (uint32_t*)((char*)d.poffs + up256(np * 8));
-  d.keys = (uint64_t*)((SD_PATHS_KEYS_TO_HOST ? pin : dev) + staged_keys_offset(pl));
-  return d;
+// A staged batch's keys: in `pin` (SD_PATHS_KEYS_TO_HOST) or on the device.
+static uint64_t* staged_keys(const StagedLayout& L, char* pin, char* dev) {
+  return (uint64_t*)((SD_PATHS_KEYS_TO_HOST ? pin : dev) + L.keys);
 }
 
 // the whole-file sub-batch's hash on stream s (K1L at job-step sizes)
-static int enqueue_packed(sd_cas_ctx* c, const Plan& pl, char* pin, char* dev, hipStream_t s) {
+static int enqueue_packed(sd_cas_ctx* c, const Plan& pl, const StagedLayout& L, char* pin, char* dev,
+                          hipStream_t s) {
   const size_t ns = pl.sampled.size(), np = pl.packed.size();
-  const StagedDev d = staged_dev(pl, pin, dev);
-  return np ? sd_cas_hash_packed_dev(c, dev + pl.sampled_bytes, d.poffs, d.plens, d.sizes + ns, np,
-                                     d.keys + ns, s)
+  return np ? sd_cas_hash_packed_dev(c, dev + L.packed, (uint64_t*)(dev + L.poffs), (uint32_t*)(dev + L.plens),
+                                     (uint64_t*)(dev + L.sizes) + ns, np, staged_keys(L, pin, dev) + ns, s)
             : SD_CAS_OK;
 }
 
-static int enqueue_hash(sd_cas_ctx* c, const Plan& pl, size_t n, char* pin, char* dev,
+static int enqueue_hash(sd_cas_ctx* c, const Plan& pl, const StagedLayout& L, char* pin, char* dev,
                         hipEvent_t done, size_t h2d_lo, size_t h2d_hi, bool packed_enqueued = false) {
   const size_t ns = pl.sampled.size();
-  const StagedDev d = staged_dev(pl, pin, dev);
-  (void)n;
+  uint64_t* keys = staged_keys(L, pin, dev);
   if (h2d_hi > h2d_lo)
     HIP_TRY(c, hipMemcpyAsync(dev + h2d_lo, pin + h2d_lo, h2d_hi - h2d_lo, hipMemcpyHostToDevice, c->copy));
   HIP_TRY(c, hipEventRecord(c->h2d_done, c->copy));
   HIP_TRY(c, hipStreamWaitEvent(c->stream, c->h2d_done, 0));
   int rc;
-  if (ns && (rc = sd_cas_hash_sampled_dev(c, dev, SAMPLED_CONTENT_LEN, d.sizes, ns, d.keys,
+  if (ns && (rc = sd_cas_hash_sampled_dev(c, dev, SAMPLED_CONTENT_LEN, (uint64_t*)(dev + L.sizes), ns, keys,
                                           c->stream)))
     return rc;
-  if (!packed_enqueued && (rc = enqueue_packed(c, pl, pin, dev, c->stream))) return rc;
+  if (!packed_enqueued && (rc = enqueue_packed(c, pl, L, pin, dev, c->stream))) return rc;
   // an early whole-file hash ran on copy2, beside the sampled one: join it
   if (packed_enqueued) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->packed_done, 0));
   if (!SD_PATHS_KEYS_TO_HOST)
-    HIP_TRY(c, hipMemcpyAsync(pin + staged_keys_offset(pl), d.keys,
+    HIP_TRY(c, hipMemcpyAsync(pin + L.keys, keys,
                               (ns + pl.packed.size()) * 8, hipMemcpyDeviceToHost, c->stream));
   if (done) HIP_TRY(c, hipEventRecord(done, c->stream));
   return SD_CAS_OK;
 }
 
-// bytes of the staging before its keys: content + sizes + poffs + plens
-static size_t staged_h2d_bytes(const Plan& pl) {
-  const size_t ns = pl.sampled.size(), np = pl.packed.size();
-  return pl.sampled_bytes + up256(pl.packed_bytes) + up256((ns + np) * 8) + up256(np * 8) + up256(np * 4);
-}
-
-static int enqueue_staged(sd_cas_ctx* c, const Plan& pl, const uint64_t* sizes, size_t n,
+static int enqueue_staged(sd_cas_ctx* c, const Plan& pl, const StagedLayout& L, const uint64_t* sizes,
                           char* pin, char* dev, hipEvent_t done) {
-  stage_meta(pl, sizes, pin);
-  return enqueue_hash(c, pl, n, pin, dev, done, 0, staged_h2d_bytes(pl));
+  stage_meta(pl, L, sizes, pin);
+  return enqueue_hash(c, pl, L, pin, dev, done, 0, L.h2d_bytes);
 }
 
-static void scatter_keys(const Plan& pl, const char* pin, uint64_t* out_keys) {
-  const uint64_t* h_keys = (const uint64_t*)(pin + staged_keys_offset(pl));
+static void scatter_keys(const Plan& pl, const StagedLayout& L, const char* pin, uint64_t* out_keys) {
+  const uint64_t* h_keys = (const uint64_t*)(pin + L.keys);
   const size_t ns = pl.sampled.size(), np = pl.packed.size();
   for (size_t k = 0; k < ns; k++) out_keys[pl.sampled[k]] = h_keys[k];
   for (size_t k = 0; k < np; k++) out_keys[pl.packed[k]] = h_keys[ns + k];
 }
 
-static size_t staged_pinned_bytes(const Plan& pl, size_t n);
-
 // One staged batch, blocking: staging at c->pinned, device copy in c->staging.
-static int run_staged(sd_cas_ctx* c, const Plan& pl, const uint64_t* sizes, size_t n,
+static int run_staged(sd_cas_ctx* c, const Plan& pl, const StagedLayout& L, const uint64_t* sizes,
                       uint64_t* out_keys) {
-  int rc = ensure(c, c->staging, staged_pinned_bytes(pl, n));
+  int rc = ensure(c, c->staging, L.bytes);
   if (rc) return rc;
-  if ((rc = enqueue_staged(c, pl, sizes, n, (char*)c->pinned, (char*)c->staging.p, nullptr)))
+  if ((rc = enqueue_staged(c, pl, L, sizes, (char*)c->pinned, (char*)c->staging.p, nullptr)))
     return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  scatter_keys(pl, (const char*)c->pinned, out_keys);
+  scatter_keys(pl, L, (const char*)c->pinned, out_keys);
   return SD_CAS_OK;
-}
-
-static size_t staged_pinned_bytes(const Plan& pl, size_t n) {
-  const size_t ns = pl.sampled.size(), np = pl.packed.size();
-  return pl.sampled_bytes + up256(pl.packed_bytes) + up256((ns + np) * 8) + up256(np * 8) +
-         up256(np * 4) + up256(n * 8);
 }
 
 int sd_cas_generate_cas_ids(sd_cas_ctx* c, const uint8_t* const* bufs, const uint64_t* buf_lens,
@@ -204,21 +185,21 @@ int sd_cas_generate_cas_ids(sd_cas_ctx* c, const uint8_t* const* bufs, const uin
   Plan pl;
   int rc = plan_batch(c, buf_lens, sizes, n, pl);
   if (rc) return rc;
-  rc = ensure_pinned(c, staged_pinned_bytes(pl, n));
+  const StagedLayout L = staged_layout(pl, n);
+  rc = ensure_pinned(c, L.bytes);
   if (rc) return rc;
   char* pin = (char*)c->pinned;
   for (size_t k = 0; k < pl.sampled.size(); k++)
     memcpy(pin + k * (size_t)SAMPLED_CONTENT_LEN, bufs[pl.sampled[k]], SAMPLED_CONTENT_LEN);
-  char* pbase = pin + pl.sampled_bytes;
-  const size_t ns = pl.sampled.size(), np = pl.packed.size();
-  const size_t content_bytes = pl.sampled_bytes + up256(pl.packed_bytes);
-  uint32_t* h_plens = (uint32_t*)(pin + content_bytes + up256((ns + np) * 8) + up256(np * 8));
+  char* pbase = pin + L.packed;
+  const size_t np = pl.packed.size();
+  uint32_t* h_plens = (uint32_t*)(pin + L.plens);
   for (size_t k = 0; k < np; k++) {
     const size_t i = pl.packed[k];
     if (buf_lens[i]) memcpy(pbase + pl.poff[k], bufs[i], buf_lens[i]);
     h_plens[k] = (uint32_t)buf_lens[i];
   }
-  return run_staged(c, pl, sizes, n, out_keys);
+  return run_staged(c, pl, L, sizes, out_keys);
 }
 
 static int cas_ids_from_paths(sd_cas_ctx* c, const char* const* paths, const uint64_t* sizes,
@@ -337,7 +318,7 @@ static int cas_ids_from_paths(sd_cas_ctx* c, const char* const* paths, const uin
     const size_t f0 = wstart[w], m = wstart[w + 1] - wstart[w];
     int rc = plan_batch(c, lens.data() + f0, psize.data() + f0, m, plans[w]);
     if (rc) return rc;
-    slot = std::max(slot, up256(staged_pinned_bytes(plans[w], m)));
+    slot = std::max(slot, up256(staged_layout(plans[w], m).bytes));
   }
   const int nslots = nw > 1 ? 2 : 1;
   int rc = ensure_pinned(c, nslots * slot);
@@ -387,9 +368,10 @@ static int cas_ids_from_paths(sd_cas_ctx* c, const char* const* paths, const uin
   auto gather = [&](size_t w, char* pin, char* dev, bool streamed) {
     const Plan& pl = plans[w];
     const size_t f0 = wstart[w], m = wstart[w + 1] - wstart[w];
+    const StagedLayout L = staged_layout(pl, m);
     const size_t ns = pl.sampled.size(), np = pl.packed.size();
-    const size_t content_bytes = pl.sampled_bytes + up256(pl.packed_bytes);
-    uint32_t* h_plens = (uint32_t*)(pin + content_bytes + up256((ns + np) * 8) + up256(np * 8));
+    const size_t content_bytes = L.sizes;  // the metadata follows the content
+    uint32_t* h_plens = (uint32_t*)(pin + L.plens);
     for (size_t k = 0; k < np; k++) h_plens[k] = (uint32_t)lens[f0 + pl.packed[k]];
     const size_t items = ns + np;
     // visit order (streamed, both kinds present): the whole files, then the sampled ones;
@@ -514,7 +496,7 @@ static int cas_ids_from_paths(sd_cas_ctx* c, const char* const* paths, const uin
       return hipSuccess;
     };
     auto pump = [&]() {
-      const size_t meta_hi = staged_h2d_bytes(pl);
+      const size_t meta_hi = L.h2d_bytes;
       if (hipMemcpyAsync(dev + content_bytes, pin + content_bytes, meta_hi - content_bytes,
                          hipMemcpyHostToDevice, c->copy) != hipSuccess)
         prc = SD_CAS_EHIP;
@@ -547,7 +529,7 @@ static int cas_ids_from_paths(sd_cas_ctx* c, const char* const* paths, const uin
             else if (hipEventRecord(c->packed_h2d, c->copy) != hipSuccess ||
                      hipStreamWaitEvent(c->copy2, c->packed_h2d, 0) != hipSuccess)
               prc = SD_CAS_EHIP;
-            else if (enqueue_packed(c, pl, pin, dev, c->copy2) != SD_CAS_OK ||
+            else if (enqueue_packed(c, pl, L, pin, dev, c->copy2) != SD_CAS_OK ||
                      hipEventRecord(c->packed_done, c->copy2) != hipSuccess)
               prc = SD_CAS_EHIP;
             packed_early = prc == SD_CAS_OK;
@@ -583,7 +565,8 @@ static int cas_ids_from_paths(sd_cas_ctx* c, const char* const* paths, const uin
   auto finish = [&](size_t w) -> int {
     const int b = (int)(w & 1);
     HIP_TRY(c, hipEventSynchronize(done[b]));
-    scatter_keys(plans[w], pin0 + b * slot, out_keys + wstart[w]);
+    scatter_keys(plans[w], staged_layout(plans[w], wstart[w + 1] - wstart[w]), pin0 + b * slot,
+                 out_keys + wstart[w]);
     return SD_CAS_OK;
   };
   for (size_t w = 0; w < nw && rc == 0; w++) {
@@ -591,6 +574,7 @@ static int cas_ids_from_paths(sd_cas_ctx* c, const char* const* paths, const uin
     if (w >= 2 && (rc = finish(w - 2))) break;  // slot b free again
     const size_t f0 = wstart[w], m = wstart[w + 1] - wstart[w];
     const bool single = nw == 1 && m >= STREAM_MIN_FILES;
+    const StagedLayout L = staged_layout(plans[w], m);
     char* pin = pin0 + b * slot;
     char* dev = dev0 + b * slot;
     if (single && SD_PATHS_ZERO_COPY) {
@@ -598,14 +582,14 @@ static int cas_ids_from_paths(sd_cas_ctx* c, const char* const* paths, const uin
       // straight over the host link and write the keys into it
       if ((rc = gather(w, pin, dev, false))) break;
       tr.mark("gather");
-      stage_meta(plans[w], psize.data() + f0, pin);
-      rc = enqueue_hash(c, plans[w], m, pin, pin, done[b], 0, 0);
+      stage_meta(plans[w], L, psize.data() + f0, pin);
+      rc = enqueue_hash(c, plans[w], L, pin, pin, done[b], 0, 0);
     } else {
-      if (single) stage_meta(plans[w], psize.data() + f0, pin);
+      if (single) stage_meta(plans[w], L, psize.data() + f0, pin);
       if ((rc = gather(w, pin, dev, single))) break;
       tr.mark("gather");
-      rc = single ? enqueue_hash(c, plans[w], m, pin, dev, done[b], 0, 0, packed_early)
-                  : enqueue_staged(c, plans[w], psize.data() + f0, m, pin, dev, done[b]);
+      rc = single ? enqueue_hash(c, plans[w], L, pin, dev, done[b], 0, 0, packed_early)
+                  : enqueue_staged(c, plans[w], L, psize.data() + f0, pin, dev, done[b]);
     }
     tr.mark("enqueue");
   }

@@ -6,7 +6,15 @@
 
 namespace sdcas {
 
-// Workspace bytes needed by radix_sort_pairs / group_keys for n keys.
+// Workspace layouts of radix_sort_pairs / group_keys / group_min_by_sort (sd_ws.h; null ws: measure only)
+struct SortWs { uint64_t* kalt; uint32_t *valt, *hist, *bsum, *rowtot; size_t bytes; };
+struct GroupWs { void* sort_ws; uint64_t* skeys; uint32_t *svals, *heads; size_t bytes; };
+struct GroupMinSortedWs {  // gws: a group_keys workspace (the two sorts; then the run-head counts)
+  void* gws; uint64_t *vkey, *k2, *skeys; uint32_t *order, *spos, *rep; size_t bytes;
+};
+SortWs sort_layout(void* ws, uint64_t n);
+GroupWs group_layout(void* ws, uint64_t n);
+GroupMinSortedWs group_min_sorted_layout(void* ws, uint64_t n);
 size_t sort_workspace_bytes(uint64_t n);
 size_t group_workspace_bytes(uint64_t n);
 
@@ -46,6 +54,24 @@ bool hash_group_supported(uint64_t n);
 // deeper partitions (tests use them to reach the > 200M-key plan shapes at small n)
 size_t hash_group_workspace_bytes(uint64_t n, uint64_t target = 0);
 size_t partition_workspace_bytes(uint64_t n, uint32_t parts);
+// hash_group_min's three chains (it picks one by n and target; each starts at ws); partition_range's ws
+struct SmallRegionsWs {  // spill: the overflow carve cursor
+  uint64_t* rkeys; uint32_t* rfile; uint64_t* gkeys; uint32_t* gvals; unsigned long long* spill;
+  uint64_t* skeys; uint32_t* sfile; size_t bytes;
+};
+struct BigRegionsWs {
+  uint64_t* rkeys; uint32_t* rfile; uint64_t* skeys; uint32_t* spos; uint64_t* k2;
+  uint32_t *p2, *starts; unsigned long long* shards; uint64_t* gkeys; uint32_t* gvals; size_t bytes;
+};
+struct HashChainWs {
+  uint64_t* k1; uint32_t* p1; uint64_t* k2; uint32_t *p2, *fill, *starts1, *starts;
+  unsigned long long* shards; uint64_t* gkeys; uint32_t* gvals; size_t bytes;
+};
+struct PartitionWs { uint32_t *totals, *fill; size_t bytes; };
+SmallRegionsWs small_regions_layout(void* ws, uint64_t n);
+BigRegionsWs big_regions_layout(void* ws, uint64_t n);
+HashChainWs hash_chain_layout(void* ws, uint64_t n, uint64_t target);
+PartitionWs partition_layout(void* ws, uint32_t parts);
 // out[i] = min{ val(j) : keys[j] == keys[i] } with val(j) = vals ? vals[j] : j;
 // *d_objects = #distinct keys (written on the device).  n < 2^32.  `totals`: a persistent
 // device buffer of GROUP_TOTALS_WORDS u32, all zero before the first call (every call leaves
@@ -59,9 +85,13 @@ hipError_t hash_group_min(const uint64_t* keys, const uint32_t* vals, uint64_t n
 // (REGIONS u32, persistent, zero between calls) is re-zeroed by the bucket tables.
 uint64_t region_capacity(uint64_t n);
 bool region_group_supported(uint64_t n);
+// a region set's buffer; objects: 2 u64 (the Object count, the overflow carve cursor)
+struct RegionGroupWs {
+  uint64_t* rkeys; uint32_t* rfile; uint64_t* gkeys; uint32_t* gvals;
+  uint64_t* spill_keys; uint32_t* spill_file; uint64_t* objects; size_t bytes;
+};
+RegionGroupWs region_group_layout(void* ws, uint64_t n);
 size_t region_group_workspace_bytes(uint64_t n);
-void region_group_layout(void* ws, uint64_t n, uint64_t** rkeys, uint32_t** rfile, uint64_t** gkeys,
-                         uint32_t** gvals, uint64_t** spill_keys, uint32_t** spill_file);
 // cursor: the set's REGION_SET_WORDS counters (sd_mix.h); d_objects: 2 u64 (count, overflow
 // carve cursor; K1G zeroed both); spill_keys/spill_file: the rows K1G could not store in
 // their region; keys/n: the batch's key array, read only if a full region's distinct keys

@@ -325,10 +325,16 @@ hipError_t sd_dispatch_sampled(sd_cas_ctx* c, const uint8_t* content, uint64_t s
 // Whole-file batch dispatch.  Small batches: K1L, a wave per file, no sort.  Otherwise K2,
 // or K1L with 4 files per wave: the files are visited by descending chunk count (one stable
 // radix pass) so the lanes of a wave (K2) / the files of a wave (K1L) match.
-// workspace (c->ws): length keys | sorted keys | order | sort workspace
+// workspace: length keys | sorted keys | order | sort workspace
+PackedWs sd_packed_layout(void* ws, size_t n) {
+  WsCarve w(ws);  PackedWs L;
+  L.lkeys = w.take<uint64_t>(n);  L.skeys = w.take<uint64_t>(n);  L.order = w.take<uint32_t>(n);
+  L.sort_ws = w.nest(sort_workspace_bytes(n));
+  L.bytes = w.bytes();  return L;
+}
 size_t sd_packed_workspace_bytes(const sd_cas_ctx* c, size_t n) {
   if (n < c->latency_packed && c->chunkpar_seg(n, false) == 64) return 0;
-  return 2 * up256(n * 8) + up256(n * 4) + sort_workspace_bytes(n);
+  return sd_packed_layout(nullptr, n).bytes;
 }
 
 hipError_t sd_dispatch_packed(sd_cas_ctx* c, const uint8_t* arena, const uint64_t* offs,
@@ -337,17 +343,14 @@ hipError_t sd_dispatch_packed(sd_cas_ctx* c, const uint8_t* arena, const uint64_
   const bool k1l = n < c->latency_packed;
   if (k1l && c->chunkpar_seg(n, false) == 64)
     return hash_chunkpar(arena, offs, 0, lens, 0, sizes, n, keys, 64, s);
-  const size_t kb = up256(n * 8), ob = up256(n * 4);
-  char* p = (char*)c->ws.p;
-  uint64_t* lkeys = (uint64_t*)p;
-  uint64_t* skeys = (uint64_t*)(p + kb);
-  uint32_t* order = (uint32_t*)(p + 2 * kb);
-  void* sws = p + 2 * kb + ob;
-  hipError_t e = length_keys(lens, n, lkeys, s);
-  if (e == hipSuccess) e = radix_sort_pairs(lkeys, nullptr, skeys, order, n, 0, length_key_bits(n), sws, s);
+  // intended aliasing: the start of c->ws, whichever call's part of it the caller acquired
+  const PackedWs L = sd_packed_layout(c->ws.p, n);
+  hipError_t e = length_keys(lens, n, L.lkeys, s);
+  if (e == hipSuccess)
+    e = radix_sort_pairs(L.lkeys, nullptr, L.skeys, L.order, n, 0, length_key_bits(n), L.sort_ws, s);
   if (e != hipSuccess) return e;
-  if (k1l) return hash_chunkpar(arena, offs, 0, lens, 0, sizes, n, keys, 16, s, order);
-  return hash_packed(arena, offs, lens, sizes, order, n, keys, s);
+  if (k1l) return hash_chunkpar(arena, offs, 0, lens, 0, sizes, n, keys, 16, s, L.order);
+  return hash_packed(arena, offs, lens, sizes, L.order, n, keys, s);
 }
 
 int sd_cas_hash_sampled_dev(sd_cas_ctx* c, const void* d_content, uint64_t stride,
@@ -441,12 +444,6 @@ static bool fused_eligible(const sd_cas_ctx* c, size_t n) {
          c->group_target == 0;
 }
 
-// region set k's buffer: rkeys | rfile | gkeys | gvals | spill keys | spill files
-// (region_group_layout) | objects u64 | overflow carve cursor u64
-static uint64_t* region_objects(sd_cas_ctx* c, int k) {
-  return (uint64_t*)((char*)c->regions[k].p + region_group_workspace_bytes(c->region_n[k]));
-}
-
 int sd_cas_hash_regions_sampled_dev(sd_cas_ctx* c, const void* d_content, uint64_t stride,
                                     const uint64_t* d_sizes, size_t n, uint64_t* d_keys,
                                     uint32_t* d_rep, uint32_t* d_overflow, void* stream) {
@@ -474,20 +471,19 @@ int sd_cas_hash_regions_sampled_dev(sd_cas_ctx* c, const void* d_content, uint64
     // set k holds the Object count of the context's last grouping, which this refill's K1G
     // zeroes: keep it in d_scalar for sd_cas_copy_objects_dev
     HIP_TRY(c, sd_ws_acquire(c, s));
-    HIP_TRY(c, hipMemcpyAsync(c->d_scalar, region_objects(c, k), 8, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->d_scalar, region_group_layout(c->regions[k].p, c->region_n[k]).objects, 8,
+                              hipMemcpyDeviceToDevice, s));
     HIP_TRY(c, sd_ws_release(c, s));
     c->region_obj_set = -1;
   }
   c->region_n[k] = n;  // sizes the layout (ensure below grows the set if needed)
-  int rc = ensure(c, c->regions[k], region_group_workspace_bytes(n) + 256);
+  int rc = ensure(c, c->regions[k], region_group_workspace_bytes(n));
   if (rc) return rc;
-  uint64_t *rkeys, *gkeys, *skeys;
-  uint32_t *rfile, *gvals, *sfile;
-  region_group_layout(c->regions[k].p, n, &rkeys, &rfile, &gkeys, &gvals, &skeys, &sfile);
+  const RegionGroupWs L = region_group_layout(c->regions[k].p, c->region_n[k]);
   uint32_t* cur = c->gcursor + REGION_SET_WORDS * k;
   hipError_t e = hash_sampled_regions((const uint8_t*)d_content, stride, d_sizes, n, d_keys, d_rep,
-                                      rkeys, rfile, cur, region_capacity(n), skeys, sfile, d_overflow,
-                                      region_objects(c, k), s, (uint32_t)(c->quantum / 256));
+                                      L.rkeys, L.rfile, cur, region_capacity(n), L.spill_keys,
+                                      L.spill_file, d_overflow, L.objects, s, (uint32_t)(c->quantum / 256));
   if (e != hipSuccess) {
     (void)hipMemsetAsync(cur, 0, REGION_SET_WORDS * 4, s);  // restore the cursors' invariant
     return fail(c, SD_CAS_EHIP, "hash_regions: %s", hipGetErrorString(e));
@@ -507,14 +503,11 @@ int sd_cas_group_regions_dev(sd_cas_ctx* c, size_t n, uint32_t* d_rep, uint64_t*
     return fail(c, SD_CAS_EINVAL, "group_regions: no ungrouped hash_regions batch of %zu files", n);
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = pick(c, stream);
-  uint64_t *rkeys, *gkeys, *skeys;
-  uint32_t *rfile, *gvals, *sfile;
-  region_group_layout(c->regions[k].p, n, &rkeys, &rfile, &gkeys, &gvals, &skeys, &sfile);
-  uint64_t* obj = region_objects(c, k);
+  const RegionGroupWs L = region_group_layout(c->regions[k].p, c->region_n[k]);
   uint32_t* cur = c->gcursor + REGION_SET_WORDS * k;
   HIP_TRY(c, hipStreamWaitEvent(s, c->region_hashed[k], 0));  // after its K1G, whatever stream
-  hipError_t e = region_group_min(rkeys, rfile, cur, region_capacity(n), d_rep, obj, gkeys, gvals,
-                                  c->region_keys[k], n, skeys, sfile, c->test_table_fill, s);
+  hipError_t e = region_group_min(L.rkeys, L.rfile, cur, region_capacity(n), d_rep, L.objects, L.gkeys, L.gvals,
+                                  c->region_keys[k], n, L.spill_keys, L.spill_file, c->test_table_fill, s);
   if (e != hipSuccess) {
     (void)hipMemsetAsync(cur, 0, REGION_SET_WORDS * 4, s);
     return fail(c, SD_CAS_EHIP, "group_regions: %s", hipGetErrorString(e));
@@ -524,7 +517,7 @@ int sd_cas_group_regions_dev(sd_cas_ctx* c, size_t n, uint32_t* d_rep, uint64_t*
   c->region_grouped[k] = true;
   c->region_obj_set = k;
   if (out_objects) {
-    HIP_TRY(c, hipMemcpyAsync(out_objects, obj, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(out_objects, L.objects, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
   }
   return SD_CAS_OK;
@@ -648,6 +641,33 @@ size_t sd_cas_identifier_max_steps(size_t n, uint32_t chunk) {
   return chunk ? (n + chunk - 1) / chunk : 0;
 }
 
+// the link emission's staging: rep | hkeys | hrows | minrow | orphans | starts | counts |
+// [event block offsets | scan tiles | key filter] | 4 counters (hashed rows, orphan rows, waves
+// with a bad Object id, events); the seeded grouping runs over the n hashed rows + the n_seed
+// existing Objects' keys.  The bracketed sections serve rows with pre-existing Objects (pre) and
+// take no room without them; such rows reuse the grouping's buffers once it is done: events
+// (hkeys / hrows), sorted events (orphans / minrow), scan elements (hkeys).
+LinkStagingWs sd_link_staging_layout(void* base, size_t n, size_t n_seed, size_t steps_total, bool pre) {
+  const size_t m = n + n_seed;
+  WsCarve w(base);  LinkStagingWs L;
+  L.rep = w.take<uint32_t>(n);  L.hkeys = w.take<uint64_t>(m);
+  L.hrows = w.take<uint32_t>(m);  L.minrow = w.take<uint32_t>(m);
+  L.orphans = w.take<uint64_t>(n);  L.starts = w.take<uint32_t>(steps_total + 1);
+  L.counts = w.take<uint32_t>(2 * steps_total);  L.boff = w.take<uint32_t>(pre ? pre_blocks(n) : 0);
+  L.tiles = w.take<uint64_t>(pre ? segmin_tiles_bytes(n) / 8 : 0);
+  L.filter = w.take<uint32_t>(pre ? pre_filter_bytes() / 4 : 0);  L.counters = w.take<uint64_t>(4);
+  L.bytes = w.bytes();  return L;
+}
+// the host forms' device copies of their arrays (c->io)
+LinkIoWs sd_link_io_layout(void* base, size_t n, size_t n_seed, bool pre) {
+  WsCarve w(base);  LinkIoWs L;
+  L.keys = w.take<uint64_t>(n);  L.state = w.take<uint8_t>(n);
+  L.step = w.take<uint32_t>(n);  L.object = w.take<uint32_t>(n);
+  L.action = w.take<uint8_t>(n);  L.seed_keys = w.take<uint64_t>(n_seed);
+  L.seed_objects = w.take<uint32_t>(n_seed);  L.pre = pre ? w.take<uint32_t>(n) : nullptr;
+  L.bytes = w.bytes();  return L;
+}
+
 int sd_cas_identifier_links_ex_dev(sd_cas_ctx* c, const uint64_t* d_keys, const uint8_t* d_state,
                                    size_t n, uint32_t chunk, const uint64_t* d_seed_keys,
                                    const uint32_t* d_seed_objects, size_t n_seed,
@@ -670,64 +690,42 @@ int sd_cas_identifier_links_ex_dev(sd_cas_ctx* c, const uint64_t* d_keys, const 
   for (size_t k = 0; k < 2 * steps_total; k++) h_step_counts[k] = 0;
   if (n == 0) return SD_CAS_OK;
   hipStream_t s = pick(c, stream);
-  // staging (this call is blocking): rep | hkeys | hrows | minrow | orphans | starts | counts |
-  // [event block offsets | scan tiles | key filter] | 4 counters; the seeded grouping runs over
-  // the hashed rows + the existing Objects' keys.  Rows with pre-existing Objects reuse the
-  // grouping's buffers once it is done: events (hkeys / hrows), sorted events (orphans /
-  // minrow), scan elements (hkeys)
-  const size_t m = n + n_seed;
-  const size_t b_rep = up256(n * 4), b_hk = up256(m * 8), b_hr = up256(m * 4), b_mr = up256(m * 4),
-               b_or = up256(n * 8), b_st = up256((steps_total + 1) * 4), b_ct = up256(steps_total * 8),
-               b_bo = d_pre_objects ? up256(pre_blocks(n) * 4) : 0,
-               b_tl = d_pre_objects ? up256(segmin_tiles_bytes(n)) : 0,
-               b_fl = d_pre_objects ? up256(pre_filter_bytes()) : 0;
+  // (this call is blocking)
   int rc = ensure(c, c->staging,
-                  b_rep + b_hk + b_hr + b_mr + b_or + b_st + b_ct + b_bo + b_tl + b_fl + 256);
+                  sd_link_staging_layout(nullptr, n, n_seed, steps_total, d_pre_objects != nullptr).bytes);
   if (rc) return rc;
-  char* p = (char*)c->staging.p;
-  uint32_t* rep = (uint32_t*)p; p += b_rep;
-  uint64_t* hkeys = (uint64_t*)p; p += b_hk;
-  uint32_t* hrows = (uint32_t*)p; p += b_hr;
-  uint32_t* minrow = (uint32_t*)p; p += b_mr;
-  uint64_t* orphans = (uint64_t*)p; p += b_or;
-  uint32_t* starts = (uint32_t*)p; p += b_st;
-  uint32_t* counts = (uint32_t*)p; p += b_ct;
-  uint32_t* boff = (uint32_t*)p; p += b_bo;
-  uint64_t* tiles = (uint64_t*)p; p += b_tl;
-  uint32_t* filter = (uint32_t*)p; p += b_fl;
-  // hashed rows | orphan rows | waves with a bad Object id | events
-  uint64_t* counters = (uint64_t*)p;
+  const LinkStagingWs L = sd_link_staging_layout(c->staging.p, n, n_seed, steps_total, d_pre_objects != nullptr);
   // 1. grouping over the hashed rows (rep = the key's first row; seeded: the lowest existing
   //    Object id when the key has one — mod.rs:180-198 finds Objects by cas over the whole
   //    library), and the rows that stay orphan after being processed (they steer the cursor)
   std::vector<uint64_t> stay;  // row << 8 | state, ascending
   if (d_state || seeded) {
     uint64_t cnt[3] = {0, 0, 0};
-    HIP_TRY(c, hipMemsetAsync(counters, 0, 32, s));
-    HIP_TRY(c, links_check_ids(d_seed_objects, n_seed, false, counters + 2, s));
-    if (d_pre_objects) HIP_TRY(c, links_check_ids(d_pre_objects, n, true, counters + 2, s));
-    HIP_TRY(c, links_split(d_keys, d_state, n, hkeys, hrows, counters, orphans, counters + 1,
+    HIP_TRY(c, hipMemsetAsync(L.counters, 0, 32, s));
+    HIP_TRY(c, links_check_ids(d_seed_objects, n_seed, false, L.counters + 2, s));
+    if (d_pre_objects) HIP_TRY(c, links_check_ids(d_pre_objects, n, true, L.counters + 2, s));
+    HIP_TRY(c, links_split(d_keys, d_state, n, L.hkeys, L.hrows, L.counters, L.orphans, L.counters + 1,
                            seeded ? LINKS_ROW_FLAG : 0u, s));
-    HIP_TRY(c, hipMemcpyAsync(cnt, counters, 24, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(cnt, L.counters, 24, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (cnt[2])
       return fail(c, SD_CAS_EINVAL, "identifier_links: an existing Object id is >= 2^31");
     stay.resize(cnt[1]);
     if (cnt[1]) {
-      HIP_TRY(c, hipMemcpyAsync(stay.data(), orphans, cnt[1] * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(c, hipMemcpyAsync(stay.data(), L.orphans, cnt[1] * 8, hipMemcpyDeviceToHost, s));
     }
     if (n_seed) {  // the existing Objects' (cas key, id) pairs after the hashed rows
-      HIP_TRY(c, hipMemcpyAsync(hkeys + cnt[0], d_seed_keys, n_seed * 8, hipMemcpyDeviceToDevice, s));
-      HIP_TRY(c, hipMemcpyAsync(hrows + cnt[0], d_seed_objects, n_seed * 4, hipMemcpyDeviceToDevice, s));
+      HIP_TRY(c, hipMemcpyAsync(L.hkeys + cnt[0], d_seed_keys, n_seed * 8, hipMemcpyDeviceToDevice, s));
+      HIP_TRY(c, hipMemcpyAsync(L.hrows + cnt[0], d_seed_objects, n_seed * 4, hipMemcpyDeviceToDevice, s));
     }
     if (cnt[0]) {
-      if ((rc = sd_cas_group_min_dev(c, hkeys, hrows, cnt[0] + n_seed, minrow, nullptr, s))) return rc;
-      HIP_TRY(c, links_scatter(minrow, hrows, cnt[0], rep, seeded ? LINKS_ROW_FLAG : 0u, s));
+      if ((rc = sd_cas_group_min_dev(c, L.hkeys, L.hrows, cnt[0] + n_seed, L.minrow, nullptr, s))) return rc;
+      HIP_TRY(c, links_scatter(L.minrow, L.hrows, cnt[0], L.rep, seeded ? LINKS_ROW_FLAG : 0u, s));
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     std::sort(stay.begin(), stay.end());
   } else {
-    if ((rc = sd_cas_group_dev(c, d_keys, n, rep, nullptr, s))) return rc;
+    if ((rc = sd_cas_group_dev(c, d_keys, n, L.rep, nullptr, s))) return rc;
   }
   // 2. the cursor walk (host; O(steps + orphans)): step k covers [start, start + chunk);
   //    the next cursor is its last row, which the next query returns again iff it is
@@ -760,32 +758,32 @@ int sd_cas_identifier_links_ex_dev(sd_cas_ctx* c, const uint64_t* d_keys, const 
   }
   const size_t nsteps = h_starts.size();
   h_starts.push_back(0xFFFFFFFFu);  // sentinel
-  HIP_TRY(c, hipMemcpyAsync(starts, h_starts.data(), h_starts.size() * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(L.starts, h_starts.data(), h_starts.size() * 4, hipMemcpyHostToDevice, s));
   // 3. rows that already own an Object (links.hip, sd_links_pre_*): the events — hashed rows
   //    of the reached steps that hold an Object — compacted in row order, sorted stably by key,
   //    and scanned; each hashed row then looks its key up in the decision kernel
   uint64_t n_ev = 0;
   if (d_pre_objects) {
-    HIP_TRY(c, links_pre_count(d_state, d_pre_objects, reached, boff, counters + 3, s));
-    HIP_TRY(c, hipMemcpyAsync(&n_ev, counters + 3, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, links_pre_count(d_state, d_pre_objects, reached, L.boff, L.counters + 3, s));
+    HIP_TRY(c, hipMemcpyAsync(&n_ev, L.counters + 3, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
   }
   if (n_ev) {
-    HIP_TRY(c, hipMemsetAsync(filter, 0, pre_filter_bytes(), s));
-    HIP_TRY(c, links_pre_emit(d_keys, d_state, d_pre_objects, reached, boff, hkeys, hrows, filter, s));
-    uint64_t* skeys = orphans;
-    uint32_t* srows = minrow;
-    if ((rc = sd_cas_sort_pairs_dev(c, hkeys, hrows, n_ev, skeys, srows, 0, 64, s))) return rc;
-    HIP_TRY(c, links_pre_scan(skeys, srows, d_pre_objects, n_ev, starts, (uint32_t)nsteps, hkeys,
-                              tiles, s));
+    HIP_TRY(c, hipMemsetAsync(L.filter, 0, pre_filter_bytes(), s));
+    HIP_TRY(c, links_pre_emit(d_keys, d_state, d_pre_objects, reached, L.boff, L.hkeys, L.hrows, L.filter, s));
+    uint64_t* skeys = L.orphans;
+    uint32_t* srows = L.minrow;
+    if ((rc = sd_cas_sort_pairs_dev(c, L.hkeys, L.hrows, n_ev, skeys, srows, 0, 64, s))) return rc;
+    HIP_TRY(c, links_pre_scan(skeys, srows, d_pre_objects, n_ev, L.starts, (uint32_t)nsteps, L.hkeys,
+                              L.tiles, s));
   }
   // 4. per-row decisions + per-step counts (device)
-  HIP_TRY(c, hipMemsetAsync(counts, 0, std::max<size_t>(nsteps, 1) * 8, s));
-  HIP_TRY(c, links_decide(d_state, rep, n, starts, (uint32_t)nsteps, reached, d_step, d_object,
-                          d_action, counts, seeded, d_keys, orphans, minrow, hkeys, filter, n_ev,
+  HIP_TRY(c, hipMemsetAsync(L.counts, 0, std::max<size_t>(nsteps, 1) * 8, s));
+  HIP_TRY(c, links_decide(d_state, L.rep, n, L.starts, (uint32_t)nsteps, reached, d_step, d_object,
+                          d_action, L.counts, seeded, d_keys, L.orphans, L.minrow, L.hkeys, L.filter, n_ev,
                           (uint32_t)chunk, s));
   std::vector<uint32_t> hc(2 * std::max<size_t>(nsteps, 1));
-  HIP_TRY(c, hipMemcpyAsync(hc.data(), counts, hc.size() * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(hc.data(), L.counts, hc.size() * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   for (size_t k = 0; k < nsteps; k++) {
     h_step_counts[2 * k] = hc[2 * k] + extra[k];
@@ -836,36 +834,25 @@ int sd_cas_identifier_links_ex(sd_cas_ctx* c, const uint64_t* h_keys, const uint
     return sd_cas_identifier_links_dev(c, nullptr, nullptr, n, chunk, nullptr, nullptr, nullptr,
                                        h_step_counts, max_steps, out_steps, c->stream);
   HIP_TRY(c, hipSetDevice(c->device));
-  // device copies (c->io): keys | state | step | object | action | seed keys | seed ids |
-  // pre-existing Objects
-  const size_t bk = up256(n * 8), bs = up256(n), b4 = up256(n * 4);
-  const size_t bsk = up256(n_seed * 8), bso = up256(n_seed * 4), bpo = h_pre_objects ? b4 : 0;
-  int rc = ensure(c, c->io, bk + 2 * bs + 2 * b4 + bsk + bso + bpo);
+  int rc = ensure(c, c->io, sd_link_io_layout(nullptr, n, n_seed, h_pre_objects != nullptr).bytes);
   if (rc) return rc;
-  char* p = (char*)c->io.p;
-  uint64_t* d_keys = (uint64_t*)p; p += bk;
-  uint8_t* d_state = h_state ? (uint8_t*)p : nullptr; p += bs;
-  uint32_t* d_step = (uint32_t*)p; p += b4;
-  uint32_t* d_object = (uint32_t*)p; p += b4;
-  uint8_t* d_action = (uint8_t*)p; p += bs;
-  uint64_t* d_seed_keys = (uint64_t*)p; p += bsk;
-  uint32_t* d_seed_objects = (uint32_t*)p; p += bso;
-  uint32_t* d_pre = h_pre_objects ? (uint32_t*)p : nullptr;
+  const LinkIoWs L = sd_link_io_layout(c->io.p, n, n_seed, h_pre_objects != nullptr);
+  uint8_t* d_state = h_state ? L.state : nullptr;
   hipStream_t s = c->stream;
-  HIP_TRY(c, hipMemcpyAsync(d_keys, h_keys, n * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(L.keys, h_keys, n * 8, hipMemcpyHostToDevice, s));
   if (h_state) HIP_TRY(c, hipMemcpyAsync(d_state, h_state, n, hipMemcpyHostToDevice, s));
   if (n_seed) {
-    HIP_TRY(c, hipMemcpyAsync(d_seed_keys, h_seed_keys, n_seed * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(d_seed_objects, h_seed_objects, n_seed * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(L.seed_keys, h_seed_keys, n_seed * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(L.seed_objects, h_seed_objects, n_seed * 4, hipMemcpyHostToDevice, s));
   }
-  if (d_pre) HIP_TRY(c, hipMemcpyAsync(d_pre, h_pre_objects, n * 4, hipMemcpyHostToDevice, s));
-  rc = sd_cas_identifier_links_ex_dev(c, d_keys, d_state, n, chunk, d_seed_keys, d_seed_objects,
-                                      n_seed, d_pre, d_step, d_object, d_action, h_step_counts,
+  if (L.pre) HIP_TRY(c, hipMemcpyAsync(L.pre, h_pre_objects, n * 4, hipMemcpyHostToDevice, s));
+  rc = sd_cas_identifier_links_ex_dev(c, L.keys, d_state, n, chunk, L.seed_keys, L.seed_objects,
+                                      n_seed, L.pre, L.step, L.object, L.action, h_step_counts,
                                       max_steps, out_steps, s);
   if (rc) return rc;
-  HIP_TRY(c, hipMemcpyAsync(h_step, d_step, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(h_object, d_object, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(h_action, d_action, n, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(h_step, L.step, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(h_object, L.object, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(h_action, L.action, n, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   return SD_CAS_OK;
 }
@@ -901,8 +888,37 @@ static_assert(SD_CAS_STAT_ROWS == STAT_ROWS && SD_CAS_STAT_OBJECTS == STAT_OBJEC
                   SD_CAS_STAT_BAD_ROWS == STAT_BAD_ROWS && SD_CAS_STAT_COUNT == STAT_COUNT,
               "stat constants");
 
-// ws: totals shards | the context's totals (d_totals NULL).  state: the host form's row
-// states (rows that are not hashed take no part).
+// ws: totals shards | the context's totals (d_totals NULL)
+StatsWs sd_stats_layout(void* ws) {
+  WsCarve w(ws);  StatsWs L;
+  L.shards = w.take<uint64_t>(stats_shard_bytes() / 8);  L.totals = w.take<uint64_t>(SD_CAS_STAT_COUNT);
+  L.bytes = w.bytes();  return L;
+}
+// top duplicates' ws: histogram | selection words | tile counts and offsets (small_bytes up to
+// here) | m candidates (~waste, head) | sorted candidates | the sort's workspace
+TopWs sd_top_layout(void* ws, uint64_t n, uint64_t m) {
+  WsCarve w(ws);  TopWs L;
+  L.hist = w.take<uint64_t>(TOP_BINS);  L.sel = w.take<uint64_t>(TOP_SEL_WORDS);
+  L.scan = w.take<uint32_t>(top_scan_bytes(n) / 4);  L.ckeys = w.take<uint64_t>(m);
+  L.cvals = w.take<uint32_t>(m);  L.skeys = w.take<uint64_t>(m);  L.svals = w.take<uint32_t>(m);
+  L.sort_ws = w.nest(m ? sort_workspace_bytes(m) : 0);
+  L.bytes = w.bytes();  return L;
+}
+// the duplicate report's device copies (c->io): keys | sizes | rep | copies | [state | hashed
+// keys | hashed rows | their minimum rows | orphan list] | top heads | top waste | 2 counters;
+// the bracketed section serves row states and is null without them
+DupReportWs sd_dup_report_layout(void* base, size_t n, bool state, size_t k) {
+  WsCarve w(base);  DupReportWs L;
+  L.keys = w.take<uint64_t>(n);  L.sizes = w.take<uint64_t>(n);
+  L.rep = w.take<uint32_t>(n);  L.copies = w.take<uint32_t>(n);
+  L.state = state ? w.take<uint8_t>(n) : nullptr;  L.hkeys = state ? w.take<uint64_t>(n) : nullptr;
+  L.hrows = state ? w.take<uint32_t>(n) : nullptr;  L.minrow = state ? w.take<uint32_t>(n) : nullptr;
+  L.orphans = state ? w.take<uint64_t>(n) : nullptr;  L.top_heads = w.take<uint32_t>(k);
+  L.top_waste = w.take<uint64_t>(k);  L.counters = w.take<uint64_t>(2);
+  L.bytes = w.bytes();  return L;
+}
+
+// state: the host form's row states (rows that are not hashed take no part).
 static int object_stats_impl(sd_cas_ctx* c, const uint32_t* d_rep, const uint64_t* d_sizes,
                              const uint8_t* d_state, size_t n, uint32_t* d_copies,
                              uint64_t* d_totals, uint64_t* out_totals, hipStream_t s) {
@@ -914,13 +930,12 @@ static int object_stats_impl(sd_cas_ctx* c, const uint32_t* d_rep, const uint64_
     }
     return SD_CAS_OK;
   }
-  const size_t b_sh = up256(stats_shard_bytes());
-  int rc = ensure(c, c->ws, b_sh + 256);
+  int rc = ensure(c, c->ws, sd_stats_layout(nullptr).bytes);
   if (rc) return rc;
-  uint64_t* shards = (uint64_t*)c->ws.p;
-  if (!d_totals) d_totals = (uint64_t*)((char*)c->ws.p + b_sh);
+  const StatsWs L = sd_stats_layout(c->ws.p);
+  if (!d_totals) d_totals = L.totals;
   HIP_TRY(c, sd_ws_acquire(c, s));
-  HIP_TRY(c, object_stats(d_rep, d_sizes, d_state, n, d_copies, d_totals, shards, s));
+  HIP_TRY(c, object_stats(d_rep, d_sizes, d_state, n, d_copies, d_totals, L.shards, s));
   if (out_totals)
     HIP_TRY(c, hipMemcpyAsync(out_totals, d_totals, SD_CAS_STAT_COUNT * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, sd_ws_release(c, s));
@@ -961,52 +976,37 @@ int sd_cas_top_duplicates_dev(sd_cas_ctx* c, const uint32_t* d_rep, const uint64
     HIP_TRY(c, hipStreamSynchronize(s));
     return SD_CAS_OK;
   }
-  // ws: histogram | selection words | tile counts and offsets | candidates (~waste, head) | sorted
-  // candidates | the sort's workspace.  The candidate count m is known only after the
-  // selection, so the first part is sized up front; if the rest does not fit, ws grows (that
-  // synchronises and drops its contents) and the selection runs once more — the steady state
-  // is one 32-byte read-back, the call's one sync before the final one.
-  const size_t b_hist = up256(TOP_BINS * 8), b_sel = up256(TOP_SEL_WORDS * 8),
-               b_off = up256(top_scan_bytes(n)), b_small = b_hist + b_sel + b_off;
-  int rc = ensure(c, c->ws, b_small);
+  // The candidate count m is known only after the selection, so the layout's first part (m = 0)
+  // is sized up front; if the rest does not fit, ws grows (that synchronises and drops its
+  // contents) and the selection runs once more — the steady state is one 32-byte read-back,
+  // the call's one sync before the final one.
+  int rc = ensure(c, c->ws, sd_top_layout(nullptr, n, 0).bytes);
   if (rc) return rc;
   HIP_TRY(c, sd_ws_acquire(c, s));
   uint64_t sel[TOP_SEL_WORDS] = {0, 0, 0, 0};
-  {
-    char* p = (char*)c->ws.p;
-    uint64_t* d_sel = (uint64_t*)(p + b_hist);
-    HIP_TRY(c, top_select(d_rep, d_sizes, d_copies, n, k, (uint64_t*)p, d_sel,
-                          (uint32_t*)(p + b_hist + b_sel), s));
-    HIP_TRY(c, hipMemcpyAsync(sel, d_sel, sizeof sel, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-  }
+  TopWs L = sd_top_layout(c->ws.p, n, 0);
+  HIP_TRY(c, top_select(d_rep, d_sizes, d_copies, n, k, L.hist, L.sel, L.scan, s));
+  HIP_TRY(c, hipMemcpyAsync(sel, L.sel, sizeof sel, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
   const uint64_t m = sel[TOP_SEL_M];
   const int top_bin = (int)sel[TOP_SEL_TOP];
-  const size_t b_k = up256(m * 8), b_v = up256(m * 4);
-  const size_t need = b_small + 2 * (b_k + b_v) + (m ? sort_workspace_bytes(m) : 0);
+  const size_t need = sd_top_layout(nullptr, n, m).bytes;
   if (need > c->ws.bytes) {
     if ((rc = ensure(c, c->ws, need))) return rc;
-    char* p = (char*)c->ws.p;
-    HIP_TRY(c, top_select(d_rep, d_sizes, d_copies, n, k, (uint64_t*)p, (uint64_t*)(p + b_hist),
-                          (uint32_t*)(p + b_hist + b_sel), s));
+    L = sd_top_layout(c->ws.p, n, 0);
+    HIP_TRY(c, top_select(d_rep, d_sizes, d_copies, n, k, L.hist, L.sel, L.scan, s));
   }
-  char* p = (char*)c->ws.p;
-  const uint64_t* d_sel = (const uint64_t*)(p + b_hist);
-  const uint32_t* scan = (const uint32_t*)(p + b_hist + b_sel);
-  p += b_small;
-  uint64_t* ckeys = (uint64_t*)p; p += b_k;
-  uint32_t* cvals = (uint32_t*)p; p += b_v;
-  uint64_t* skeys = (uint64_t*)p; p += b_k;
-  uint32_t* svals = (uint32_t*)p; p += b_v;
+  L = sd_top_layout(c->ws.p, n, m);
+  uint64_t* skeys = L.skeys;  uint32_t* svals = L.svals;
   const uint64_t found = std::min<uint64_t>(k, m);
   if (m) {
-    HIP_TRY(c, top_emit(d_rep, d_sizes, d_copies, n, d_sel, scan, ckeys, cvals, s));
+    HIP_TRY(c, top_emit(d_rep, d_sizes, d_copies, n, L.sel, L.scan, L.ckeys, L.cvals, s));
     // every candidate's waste is below 2^top_bin, so ~waste differs in bits [0, top_bin) only
     if (m > 1 && top_bin > 0) {
-      HIP_TRY(c, radix_sort_pairs(ckeys, cvals, skeys, svals, m, 0, top_bin, p, s));
+      HIP_TRY(c, radix_sort_pairs(L.ckeys, L.cvals, skeys, svals, m, 0, top_bin, L.sort_ws, s));
     } else {
-      skeys = ckeys;
-      svals = cvals;
+      skeys = L.ckeys;
+      svals = L.cvals;
     }
   }
   HIP_TRY(c, top_write(skeys, svals, found, k, d_top_heads, d_top_waste, s));
@@ -1036,65 +1036,44 @@ int sd_cas_duplicate_report(sd_cas_ctx* c, const uint64_t* h_keys, const uint64_
     return SD_CAS_OK;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  // device copies (c->io): keys | sizes | state | rep | copies | hashed keys | hashed rows |
-  // their minimum rows | orphan list | top heads | top waste | 2 counters
-  const size_t b8 = up256(n * 8), b4 = up256(n * 4), b1 = up256(n);
-  const size_t kk = want_top ? k : 0, bth = up256(kk * 4), btw = up256(kk * 8);
-  const size_t bst = h_state ? b1 + b8 + 2 * b4 + b8 : 0;
-  int rc = ensure(c, c->io, 2 * b8 + 2 * b4 + bst + bth + btw + 256);
+  const size_t kk = want_top ? k : 0;
+  int rc = ensure(c, c->io, sd_dup_report_layout(nullptr, n, h_state != nullptr, kk).bytes);
   if (rc) return rc;
-  char* p = (char*)c->io.p;
-  uint64_t* d_keys = (uint64_t*)p; p += b8;
-  uint64_t* d_sizes = (uint64_t*)p; p += b8;
-  uint32_t* d_rep = (uint32_t*)p; p += b4;
-  uint32_t* d_copies = (uint32_t*)p; p += b4;
-  uint8_t* d_state = nullptr;
-  uint64_t *hkeys = nullptr, *orphans = nullptr;
-  uint32_t *hrows = nullptr, *minrow = nullptr;
-  if (h_state) {
-    d_state = (uint8_t*)p; p += b1;
-    hkeys = (uint64_t*)p; p += b8;
-    hrows = (uint32_t*)p; p += b4;
-    minrow = (uint32_t*)p; p += b4;
-    orphans = (uint64_t*)p; p += b8;
-  }
-  uint32_t* d_th = (uint32_t*)p; p += bth;
-  uint64_t* d_tw = (uint64_t*)p; p += btw;
-  uint64_t* counters = (uint64_t*)p;
+  const DupReportWs L = sd_dup_report_layout(c->io.p, n, h_state != nullptr, kk);
   hipStream_t s = c->stream;
-  HIP_TRY(c, hipMemcpyAsync(d_keys, h_keys, n * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemcpyAsync(d_sizes, h_sizes, n * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(L.keys, h_keys, n * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(L.sizes, h_sizes, n * 8, hipMemcpyHostToDevice, s));
   if (h_state) {
     // the hashed rows compacted as (key, row) pairs, grouped by the minimum row per key and
     // scattered back: rep in the CALLER's numbering, SD_CAS_NO_OBJECT on every other row
     uint64_t cnt[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(d_state, h_state, n, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(counters, 0, 16, s));
-    HIP_TRY(c, hipMemsetAsync(d_rep, 0xFF, n * 4, s));
-    HIP_TRY(c, links_split(d_keys, d_state, n, hkeys, hrows, counters, orphans, counters + 1, 0u, s));
-    HIP_TRY(c, hipMemcpyAsync(cnt, counters, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(L.state, h_state, n, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(L.counters, 0, 16, s));
+    HIP_TRY(c, hipMemsetAsync(L.rep, 0xFF, n * 4, s));
+    HIP_TRY(c, links_split(L.keys, L.state, n, L.hkeys, L.hrows, L.counters, L.orphans, L.counters + 1, 0u, s));
+    HIP_TRY(c, hipMemcpyAsync(cnt, L.counters, 16, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     if (cnt[0]) {
-      if ((rc = sd_cas_group_min_dev(c, hkeys, hrows, cnt[0], minrow, nullptr, s))) return rc;
-      HIP_TRY(c, links_scatter(minrow, hrows, cnt[0], d_rep, 0u, s));
+      if ((rc = sd_cas_group_min_dev(c, L.hkeys, L.hrows, cnt[0], L.minrow, nullptr, s))) return rc;
+      HIP_TRY(c, links_scatter(L.minrow, L.hrows, cnt[0], L.rep, 0u, s));
     }
   } else {
-    if ((rc = sd_cas_group_dev(c, d_keys, n, d_rep, nullptr, s))) return rc;
+    if ((rc = sd_cas_group_dev(c, L.keys, n, L.rep, nullptr, s))) return rc;
   }
   uint64_t totals[SD_CAS_STAT_COUNT];
-  if ((rc = object_stats_impl(c, d_rep, d_sizes, d_state, n, d_copies, nullptr, totals, s))) return rc;
+  if ((rc = object_stats_impl(c, L.rep, L.sizes, L.state, n, L.copies, nullptr, totals, s))) return rc;
   if (out_totals)
     for (int j = 0; j < SD_CAS_STAT_COUNT; j++) out_totals[j] = totals[j];
   if (want_top) {
-    if ((rc = sd_cas_top_duplicates_dev(c, d_rep, d_sizes, d_copies, n, k, d_th, d_tw, out_found, s)))
+    if ((rc = sd_cas_top_duplicates_dev(c, L.rep, L.sizes, L.copies, n, k, L.top_heads, L.top_waste, out_found, s)))
       return rc;
     if (k) {
-      HIP_TRY(c, hipMemcpyAsync(h_top_heads, d_th, k * 4, hipMemcpyDeviceToHost, s));
-      HIP_TRY(c, hipMemcpyAsync(h_top_waste, d_tw, k * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(c, hipMemcpyAsync(h_top_heads, L.top_heads, k * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(c, hipMemcpyAsync(h_top_waste, L.top_waste, k * 8, hipMemcpyDeviceToHost, s));
     }
   }
-  if (h_rep) HIP_TRY(c, hipMemcpyAsync(h_rep, d_rep, n * 4, hipMemcpyDeviceToHost, s));
-  if (h_copies) HIP_TRY(c, hipMemcpyAsync(h_copies, d_copies, n * 4, hipMemcpyDeviceToHost, s));
+  if (h_rep) HIP_TRY(c, hipMemcpyAsync(h_rep, L.rep, n * 4, hipMemcpyDeviceToHost, s));
+  if (h_copies) HIP_TRY(c, hipMemcpyAsync(h_copies, L.copies, n * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   return SD_CAS_OK;
 }

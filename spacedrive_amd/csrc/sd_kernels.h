@@ -56,10 +56,9 @@ int length_key_bits(uint64_t n);  // significant bits of the length_keys sort ke
 // 4: misaligned or past arena_bytes), counters[1] = sampled files, lens32[i] = lens[i] for a
 // whole file (<= 100 KiB) and 0 for a sampled or rejected one, sampled_idx = the sampled
 // files.  hash_inplace_sampled = K1P over such a list: keys[idx[k]] for k < n_idx.
+struct InplaceWs { uint32_t *counters, *lens32, *sampled_idx; size_t bytes; };
+InplaceWs inplace_layout(void* ws, uint64_t n);  // ws == nullptr: measure only (sd_ws.h)
 size_t inplace_workspace_bytes(uint64_t n);
-uint32_t* inplace_counters(void* ws);
-uint32_t* inplace_lens32(void* ws);
-uint32_t* inplace_sampled_idx(void* ws, uint64_t n);
 hipError_t inplace_classify(uint64_t arena_bytes, const uint64_t* offs, const uint64_t* lens,
                             uint64_t n, void* ws, hipStream_t s);
 hipError_t hash_inplace_sampled(const uint8_t* arena, const uint64_t* offs, const uint64_t* lens,

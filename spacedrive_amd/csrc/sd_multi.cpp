@@ -58,32 +58,16 @@ static thread_local std::string g_create_err;
                                          ": " + hipGetErrorString(e_));                     \
   } while (0)
 
-// per-shard exchange buffers in ctx->small
-struct Bufs {
-  uint64_t* skeys; uint32_t* sidx; uint64_t* gidx; uint64_t* splits; uint64_t* back;
-  uint64_t* rkeys; uint64_t* ridx; uint64_t* k2; uint32_t* pos; uint32_t* rep_pos; uint64_t* repg;
-};
-
-static size_t bufs_bytes(size_t n, size_t m, int G) {
-  return up256(n * 8) + up256(n * 4) + up256(n * 8) + up256((G + 1) * 8) + up256(n * 8) +
-         up256(m * 8) * 2 + up256(m * 8) + up256(m * 4) * 2 + up256(m * 8) + 256;
-}
-
-static Bufs carve(void* base, size_t n, size_t m, int G) {
-  char* p = (char*)base;
-  Bufs b;
-  b.skeys = (uint64_t*)p; p += up256(n * 8);
-  b.sidx = (uint32_t*)p; p += up256(n * 4);
-  b.gidx = (uint64_t*)p; p += up256(n * 8);
-  b.splits = (uint64_t*)p; p += up256((G + 1) * 8);
-  b.back = (uint64_t*)p; p += up256(n * 8);
-  b.rkeys = (uint64_t*)p; p += up256(m * 8);
-  b.ridx = (uint64_t*)p; p += up256(m * 8);
-  b.k2 = (uint64_t*)p; p += up256(m * 8);
-  b.pos = (uint32_t*)p; p += up256(m * 4);
-  b.rep_pos = (uint32_t*)p; p += up256(m * 4);
-  b.repg = (uint64_t*)p;
-  return b;
+// per-shard exchange buffers in ctx->small: n own keys, m received rows, G shards
+MultiBufs sd_multi_bufs_layout(void* base, size_t n, size_t m, int G) {
+  WsCarve w(base);  MultiBufs b;
+  b.skeys = w.take<uint64_t>(n);  b.sidx = w.take<uint32_t>(n);
+  b.gidx = w.take<uint64_t>(n);  b.splits = w.take<uint64_t>(G + 1);
+  b.back = w.take<uint64_t>(n);  b.rkeys = w.take<uint64_t>(m);
+  b.ridx = w.take<uint64_t>(m);  b.k2 = w.take<uint64_t>(m);
+  b.pos = w.take<uint32_t>(m);  b.rep_pos = w.take<uint32_t>(m);  b.repg = w.take<uint64_t>(m);
+  w.skip(256);  // reserve nobody reads
+  b.bytes = w.bytes();  return b;
 }
 
 extern "C" {
@@ -182,8 +166,8 @@ int sd_cas_multi_group(sd_cas_multi* m, const uint64_t* const* d_keys, const siz
     sd_cas_ctx* c = m->ctx[i];
     MHIP(m, i, hipSetDevice(c->device));
     // receive side unknown yet: size for n_i now, regrow after the counts are known
-    MTRY(m, i, sd_ensure(c, c->small, bufs_bytes(n[i], n[i], G)));
-    Bufs b = carve(c->small.p, n[i], n[i], G);
+    MTRY(m, i, sd_ensure(c, c->small, sd_multi_bufs_layout(nullptr, n[i], n[i], G).bytes));
+    MultiBufs b = sd_multi_bufs_layout(c->small.p, n[i], n[i], G);
     if (n[i]) MTRY(m, i, sd_cas_sort_pairs_dev(c, d_keys[i], nullptr, n[i], b.skeys, b.sidx, 0, 64, c->stream));
     MHIP(m, i, multi_splits(b.skeys, n[i], (uint32_t)G, b.splits, c->stream));
     MHIP(m, i, multi_gidx(b.sidx, n[i], file0[i], b.gidx, c->stream));
@@ -203,12 +187,13 @@ int sd_cas_multi_group(sd_cas_multi* m, const uint64_t* const* d_keys, const siz
   // grow the exchange buffers to the received sizes (keeps the sorted data: copy it over)
   for (int i = 0; i < G; i++) {
     sd_cas_ctx* c = m->ctx[i];
-    const size_t need = bufs_bytes(n[i], recv[i], G);
+    const size_t need = sd_multi_bufs_layout(nullptr, n[i], recv[i], G).bytes;
     if (need > c->small.bytes) {
       MHIP(m, i, hipSetDevice(c->device));
       DevBuf nb;
       MTRY(m, i, sd_ensure(c, nb, need));
-      Bufs ob = carve(c->small.p, n[i], n[i], G), nw = carve(nb.p, n[i], recv[i], G);
+      MultiBufs ob = sd_multi_bufs_layout(c->small.p, n[i], n[i], G),
+                nw = sd_multi_bufs_layout(nb.p, n[i], recv[i], G);
       MHIP(m, i, hipMemcpyAsync(nw.skeys, ob.skeys, n[i] * 8, hipMemcpyDeviceToDevice, c->stream));
       MHIP(m, i, hipMemcpyAsync(nw.sidx, ob.sidx, n[i] * 4, hipMemcpyDeviceToDevice, c->stream));
       MHIP(m, i, hipMemcpyAsync(nw.gidx, ob.gidx, n[i] * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -217,9 +202,9 @@ int sd_cas_multi_group(sd_cas_multi* m, const uint64_t* const* d_keys, const siz
       c->small = nb;
     }
   }
-  std::vector<Bufs> B(G);
+  std::vector<MultiBufs> B(G);
   for (int i = 0; i < G; i++) {
-    B[i] = carve(m->ctx[i]->small.p, n[i], recv[i], G);
+    B[i] = sd_multi_bufs_layout(m->ctx[i]->small.p, n[i], recv[i], G);
     MHIP(m, i, hipSetDevice(m->ctx[i]->device));
     MHIP(m, i, hipEventRecord(m->ev_a[i], m->ctx[i]->stream));
   }
@@ -433,8 +418,7 @@ int sd_cas_copy_objects_dev(sd_cas_ctx* c, uint64_t* d_dst, void* stream) {
   const int k = c->region_obj_set;
   if (k >= 0) {  // the fused chain's last grouping: its region set's counter, after its tables
     HIP_TRY(c, hipStreamWaitEvent(s, c->region_done[k], 0));
-    const uint64_t* obj = (const uint64_t*)((const char*)c->regions[k].p +
-                                            sdcas::region_group_workspace_bytes(c->region_n[k]));
+    const uint64_t* obj = sdcas::region_group_layout(c->regions[k].p, c->region_n[k]).objects;
     HIP_TRY(c, hipMemcpyAsync(d_dst, obj, 8, hipMemcpyDeviceToDevice, s));
     // the set's next refill (its K1G zeroes this counter) must also wait for this copy
     HIP_TRY(c, hipEventRecord(c->region_done[k], s));

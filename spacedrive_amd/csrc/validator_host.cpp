@@ -197,7 +197,7 @@ static int file_checksums_pieces(sd_cas_ctx* c, const char* const* paths, const 
   if ((rc = ensure_pinned(c, pl.slots * pl.slot_bytes)) || (rc = ensure(c, c->staging, pl.slots * pl.slot_bytes)))
     return rc;
   if ((rc = ensure(c, c->ws, std::max({checksum_workspace_bytes(cap), checksum_workspace_bytes(1 << 20),
-                                        2 * up256((maxreal + 255) / 256 * 32) + 512}))))
+                                        reduce_cvs_workspace_bytes(maxreal)}))))
     return rc;
   if ((rc = cv_capacity(c, c->cvbuf, ncv + nf, s))) return rc;  // CVs, then the digests
   uint32_t* d_cv = (uint32_t*)c->cvbuf.p;
@@ -342,8 +342,7 @@ static int file_checksum_seq(sd_cas_ctx* c, int fd, const char* path, uint8_t di
   if (rc == SD_CAS_OK) {
     uint32_t* d_out = (uint32_t*)c->d_scalar;
     hipError_t e = hipSuccess;
-    // reduce_cvs_device ping-pongs ceil(nseg / 256) CVs per level through ws
-    if (nseg > 1) rc = ensure(c, c->ws, 2 * up256((nseg + 255) / 256 * 32) + 512);
+    if (nseg > 1) rc = ensure(c, c->ws, reduce_cvs_workspace_bytes(nseg));
     if (rc == SD_CAS_OK) {
       if (nseg == 1) e = hipMemcpyAsync(d_out, c->cvbuf.p, 32, hipMemcpyDeviceToDevice, s);
       else e = reduce_cvs_device((uint32_t*)c->cvbuf.p, nseg, d_out, c->ws.p, s);
@@ -432,11 +431,10 @@ int sd_cas_checksums_dev(sd_cas_ctx* c, const void* d_arena, uint64_t arena_byte
 static hipError_t contents_hash_classified(sd_cas_ctx* c, const uint8_t* arena, const uint64_t* offs,
                                            const uint64_t* lens, size_t n, size_t n_sampled,
                                            uint64_t* keys, hipStream_t s) {
-  void* iw = c->inplace.p;
+  const InplaceWs iw = inplace_layout(c->inplace.p, n);
   hipError_t e = hipSuccess;
-  if (n_sampled < n) e = sd_dispatch_packed(c, arena, offs, inplace_lens32(iw), lens, n, keys, s);
-  if (e == hipSuccess)
-    e = hash_inplace_sampled(arena, offs, lens, inplace_sampled_idx(iw, n), n_sampled, keys, s);
+  if (n_sampled < n) e = sd_dispatch_packed(c, arena, offs, iw.lens32, lens, n, keys, s);
+  if (e == hipSuccess) e = hash_inplace_sampled(arena, offs, lens, iw.sampled_idx, n_sampled, keys, s);
   return e;
 }
 
@@ -462,7 +460,7 @@ static int contents_dev(sd_cas_ctx* c, const char* what, const void* d_arena, ui
   uint32_t verdict[2] = {0, 0};  // bad flags, sampled files
   HIP_TRY(c, sd_ws_acquire(c, s));
   HIP_TRY(c, inplace_classify(arena_bytes, d_offs, d_lens, n, c->inplace.p, s));
-  HIP_TRY(c, hipMemcpyAsync(verdict, inplace_counters(c->inplace.p), 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(verdict, inplace_layout(c->inplace.p, n).counters, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   if (verdict[0]) {
     (void)sd_ws_release(c, s);
