@@ -6,9 +6,21 @@
 // + 4x v_alignbit_b32 (rotate), so a full compression is ~680 VALU instructions with
 // the message schedule resolved at compile time (no permutation moves).  There is no
 // MFMA here: BLAKE3 is integer ARX, not a contraction.
+//
+// The header also compiles for the host (tests/native/lane_walker_test.cpp walks whole
+// messages on the CPU under sanitizers): every function is SD_B3_HD, and the one HIP builtin,
+// the rotate, has a portable form there.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define SD_B3_HD __host__ __device__ __forceinline__
+#define SD_B3_CONST __device__ constexpr
+#else
+#define SD_B3_HD inline __attribute__((always_inline))
+#define SD_B3_CONST constexpr
+#endif
 
 namespace sdcas {
 
@@ -21,15 +33,15 @@ enum : uint32_t {
   CHUNK_LEN = 1024u,
 };
 
-__device__ constexpr uint32_t IV0 = 0x6A09E667u, IV1 = 0xBB67AE85u, IV2 = 0x3C6EF372u,
-                              IV3 = 0xA54FF53Au, IV4 = 0x510E527Fu, IV5 = 0x9B05688Cu,
-                              IV6 = 0x1F83D9ABu, IV7 = 0x5BE0CD19u;
+SD_B3_CONST uint32_t IV0 = 0x6A09E667u, IV1 = 0xBB67AE85u, IV2 = 0x3C6EF372u,
+                     IV3 = 0xA54FF53Au, IV4 = 0x510E527Fu, IV5 = 0x9B05688Cu,
+                     IV6 = 0x1F83D9ABu, IV7 = 0x5BE0CD19u;
 
 // message word schedule per round (permutation applied r times), resolved at compile time
 struct Sched {
   uint8_t s[7][16];
 };
-__host__ __device__ constexpr Sched make_sched() {
+constexpr Sched make_sched() {
   Sched z{};
   const uint8_t perm[16] = {2, 6, 3, 10, 7, 0, 4, 13, 1, 11, 12, 5, 9, 14, 15, 8};
   for (int i = 0; i < 16; i++) z.s[0][i] = (uint8_t)i;
@@ -39,8 +51,12 @@ __host__ __device__ constexpr Sched make_sched() {
 }
 constexpr Sched SCHED = make_sched();
 
-__device__ __forceinline__ uint32_t rotr(uint32_t x, uint32_t n) {
+SD_B3_HD uint32_t rotr(uint32_t x, uint32_t n) {
+#if defined(__HIP_DEVICE_COMPILE__)
   return __builtin_amdgcn_alignbit(x, x, n);
+#else
+  return (x >> n) | (x << ((32u - n) & 31u));
+#endif
 }
 
 #define SDCAS_G(a, b, c, d, x, y)   \
@@ -54,7 +70,7 @@ __device__ __forceinline__ uint32_t rotr(uint32_t x, uint32_t n) {
   b = rotr(b ^ c, 7);
 
 template <int R>
-__device__ __forceinline__ void round_fn(uint32_t& v0, uint32_t& v1, uint32_t& v2, uint32_t& v3,
+SD_B3_HD void round_fn(uint32_t& v0, uint32_t& v1, uint32_t& v2, uint32_t& v3,
                                          uint32_t& v4, uint32_t& v5, uint32_t& v6, uint32_t& v7,
                                          uint32_t& v8, uint32_t& v9, uint32_t& v10, uint32_t& v11,
                                          uint32_t& v12, uint32_t& v13, uint32_t& v14, uint32_t& v15,
@@ -72,7 +88,7 @@ __device__ __forceinline__ void round_fn(uint32_t& v0, uint32_t& v1, uint32_t& v
 
 // cv <- first 8 output words of compress(cv, m, counter, blen, flags).
 // counter_hi is always 0 on this path (chunk index < 2^32, i.e. files < 4 TiB per tree).
-__device__ __forceinline__ void compress(uint32_t (&cv)[8], const uint32_t (&m)[16],
+SD_B3_HD void compress(uint32_t (&cv)[8], const uint32_t (&m)[16],
                                          uint32_t counter_lo, uint32_t counter_hi,
                                          uint32_t blen, uint32_t flags) {
   uint32_t v0 = cv[0], v1 = cv[1], v2 = cv[2], v3 = cv[3];
@@ -90,13 +106,13 @@ __device__ __forceinline__ void compress(uint32_t (&cv)[8], const uint32_t (&m)[
   cv[4] = v4 ^ v12; cv[5] = v5 ^ v13; cv[6] = v6 ^ v14; cv[7] = v7 ^ v15;
 }
 
-__device__ __forceinline__ void set_iv(uint32_t (&cv)[8]) {
+SD_B3_HD void set_iv(uint32_t (&cv)[8]) {
   cv[0] = IV0; cv[1] = IV1; cv[2] = IV2; cv[3] = IV3;
   cv[4] = IV4; cv[5] = IV5; cv[6] = IV6; cv[7] = IV7;
 }
 
 // parent node: cv <- compress(IV, left || right, 0, 64, PARENT | extra)
-__device__ __forceinline__ void parent(uint32_t (&cv)[8], const uint32_t (&left)[8],
+SD_B3_HD void parent(uint32_t (&cv)[8], const uint32_t (&left)[8],
                                        const uint32_t (&right)[8], uint32_t extra_flags) {
   uint32_t m[16];
 #pragma unroll
@@ -106,7 +122,7 @@ __device__ __forceinline__ void parent(uint32_t (&cv)[8], const uint32_t (&left)
 }
 
 // cas key = big-endian u64 of the first 8 digest bytes (digest words are little-endian)
-__device__ __forceinline__ uint64_t key_of(const uint32_t (&cv)[8]) {
+SD_B3_HD uint64_t key_of(const uint32_t (&cv)[8]) {
   return ((uint64_t)__builtin_bswap32(cv[0]) << 32) | (uint64_t)__builtin_bswap32(cv[1]);
 }
 

@@ -23,7 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "blake3_device.hpp"
+#include "blake3_lane.hpp"
 #include "sd_kernels.h"
 #include "sd_mix.h"
 #include "sd_segment_merge.h"
@@ -41,57 +41,16 @@ constexpr uint32_t SAMPLED_PAIRS = SAMPLED_CONTENT_LEN / 128;  // 448
 constexpr uint32_t SAMPLED_CHUNKS = SAMPLED_CONTENT_LEN / 1024;  // 56 full chunks
 static_assert(SAMPLED_PAIRS == 8 * SAMPLED_CHUNKS, "the sampled content is whole chunks of 8 lines");
 
-// One 128-B line (block pair P) of the lane's content: 8 x dwordx4 issued back to back.
-// (The A/B variants — non-temporal loads, 1.6x slower; 64-file tiled LINE / QUAD layouts —
-// live in tools/ubench_k1.hip with their measurements.)
-__device__ __forceinline__ void load_pair(const uint4* __restrict__ q, uint32_t P, uint4 (&buf)[8]) {
-  const uint4* p = q + 8u * P;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) buf[i] = p[i];
-}
-
-// Compress message blocks 2P and 2P+1 of chunk `ctr` from the line in A; the 2-word
-// carry is the tail of the previous line (the 8-byte size prefix shift).
-__device__ __forceinline__ void compress_pair(uint32_t (&cv)[8], const uint4 (&A)[8],
-                                              uint32_t& c0, uint32_t& c1, uint32_t ctr,
-                                              uint32_t f0, uint32_t f1) {
-  {
-    const uint32_t m[16] = {c0, c1, A[0].x, A[0].y, A[0].z, A[0].w, A[1].x, A[1].y,
-                            A[1].z, A[1].w, A[2].x, A[2].y, A[2].z, A[2].w, A[3].x, A[3].y};
-    compress(cv, m, ctr, 0u, BLOCK_LEN, f0);
-  }
-  {
-    const uint32_t m[16] = {A[3].z, A[3].w, A[4].x, A[4].y, A[4].z, A[4].w, A[5].x, A[5].y,
-                            A[5].z, A[5].w, A[6].x, A[6].y, A[6].z, A[6].w, A[7].x, A[7].y};
-    compress(cv, m, ctr, 0u, BLOCK_LEN, f1);
-  }
-  c0 = A[7].z;
-  c1 = A[7].w;
-}
-
-// load_pair pinned where the source puts it: the machine scheduler otherwise sinks a line's
+// line() pinned where the source puts it: the machine scheduler otherwise sinks a line's
 // loads down the basic block towards the next line's (same base register), which takes the
 // lead that K1's schedule below is built for away again.
+// (The A/B variants of the load — non-temporal loads, 1.6x slower; 64-file tiled LINE / QUAD
+// layouts — live in tools/ubench_k1.hip with their measurements.)
 __device__ __forceinline__ void load_pair_here(const uint4* __restrict__ q, uint32_t P,
                                                uint4 (&buf)[8]) {
   __builtin_amdgcn_sched_barrier(0);
-  load_pair(q, P, buf);
+  line(q, P, buf);
   __builtin_amdgcn_sched_barrier(0);
-}
-
-// compress_pair's two blocks separately: the first block of line P (its 2-word carry c0, c1
-// is the tail of line P - 1), and the second.
-__device__ __forceinline__ void compress_lo(uint32_t (&cv)[8], const uint4 (&A)[8], uint32_t c0,
-                                            uint32_t c1, uint32_t ctr, uint32_t f) {
-  const uint32_t m[16] = {c0, c1, A[0].x, A[0].y, A[0].z, A[0].w, A[1].x, A[1].y,
-                          A[1].z, A[1].w, A[2].x, A[2].y, A[2].z, A[2].w, A[3].x, A[3].y};
-  compress(cv, m, ctr, 0u, BLOCK_LEN, f);
-}
-__device__ __forceinline__ void compress_hi(uint32_t (&cv)[8], const uint4 (&A)[8], uint32_t ctr,
-                                            uint32_t f) {
-  const uint32_t m[16] = {A[3].z, A[3].w, A[4].x, A[4].y, A[4].z, A[4].w, A[5].x, A[5].y,
-                          A[5].z, A[5].w, A[6].x, A[6].y, A[6].z, A[6].w, A[7].x, A[7].y};
-  compress(cv, m, ctr, 0u, BLOCK_LEN, f);
 }
 
 // The 5-deep chaining-value stack lives in LDS, word-major [depth][word][thread] so every
@@ -102,37 +61,15 @@ constexpr int SAMPLED_DEPTH = 5;  // popcount(55) pending subtrees at most
 constexpr int SAMPLED_BLOCK = 512;  // 256: 1-2 % slower, 128: 4 % (profiles/r01_k1_block_ab.log)
 
 template <int B = SAMPLED_BLOCK>
-struct LdsStack {
-  uint32_t (*s)[8][B];
-  uint32_t t;
-  uint32_t sp = 0;  // wave-uniform on the sampled path
-  __device__ __forceinline__ void push(const uint32_t (&cv)[8]) {
-#pragma unroll
-    for (int w = 0; w < 8; ++w) s[sp][w][t] = cv[w];
-    ++sp;
-  }
-  __device__ __forceinline__ void pop(uint32_t (&out)[8]) {
-    --sp;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) out[w] = s[sp][w][t];
-  }
-};
+using LdsStack = CvStack<B, false>;  // sp is wave-uniform on the sampled path
 
 template <int BLK = SAMPLED_BLOCK>
 __device__ __forceinline__ uint64_t cas_lane_sampled(const uint4* __restrict__ q, uint64_t size,
                                                      LdsStack<BLK>& stk) {
   uint4 A[8], B[8];
   uint32_t cv[8];
-  // left-balanced tree: merge while the completed-chunk count has trailing zeros
-  auto merge_push = [&](uint32_t total) {
-    while ((total & 1u) == 0u) {
-      uint32_t left[8];
-      stk.pop(left);
-      parent(cv, left, cv, 0u);
-      total >>= 1;
-    }
-    stk.push(cv);
-  };
+  // (through a lambda: called directly, the inliner's order changes and with it K1's code)
+  auto push_chunk = [&](uint32_t total) { merge_push(stk, cv, total); };
   // The 448 lines are one flat sequence through two buffers, each refilled IN PLACE: A holds
   // the even lines and B the odd ones, and a buffer's next line is requested one compression
   // after its last block, once the first block of the OTHER buffer's line has read the
@@ -144,29 +81,29 @@ __device__ __forceinline__ uint64_t cas_lane_sampled(const uint4* __restrict__ q
   // and it measured slower than this (profiles/k1_pipeline/).
   B[7].z = (uint32_t)size;  // the carry into line 0: the le64(size) prefix
   B[7].w = (uint32_t)(size >> 32);
-  load_pair(q, 0, A);
+  line(q, 0, A);
   for (uint32_t c = 0;; ++c) {
     set_iv(cv);
 #pragma unroll 1
     for (uint32_t pp = 0; pp < 4; ++pp) {  // 4 x (line in A, line in B) = 16 blocks
       const uint32_t P = 8u * c + 2u * pp;
-      compress_lo(cv, A, B[7].z, B[7].w, c, pp == 0 ? (uint32_t)CHUNK_START : 0u);
+      compress_lo<PREFIXED>(cv, A, B[7].z, B[7].w, c, pp == 0 ? (uint32_t)CHUNK_START : 0u);
       load_pair_here(q, P + 1, B);  // P is even and < 448: so is P + 1
-      compress_hi(cv, A, c, 0u);
-      compress_lo(cv, B, A[7].z, A[7].w, c, 0u);
+      compress_hi<PREFIXED>(cv, A, c, 0u);
+      compress_lo<PREFIXED>(cv, B, A[7].z, A[7].w, c, 0u);
       // Wave-uniform guard: no line >= 448 is ever requested (a batch's last row may end
       // with its allocation).  It is the loop's EXIT and not a branch around the loads: a
       // conditional load joins the old and the new buffer in a phi, which came out as a
       // second buffer and 64 v_mov_b64 per iteration (152 VGPRs, 3 waves per SIMD).
       if (P + 2u >= SAMPLED_PAIRS) goto last_block;
       load_pair_here(q, P + 2, A);
-      compress_hi(cv, B, c, pp == 3 ? (uint32_t)CHUNK_END : 0u);
+      compress_hi<PREFIXED>(cv, B, c, pp == 3 ? (uint32_t)CHUNK_END : 0u);
     }
-    merge_push(c + 1);
+    push_chunk(c + 1);
   }
 last_block:  // line 447 is in B; nothing is left to request
-  compress_hi(cv, B, SAMPLED_CHUNKS - 1, CHUNK_END);
-  merge_push(SAMPLED_CHUNKS);
+  compress_hi<PREFIXED>(cv, B, SAMPLED_CHUNKS - 1, CHUNK_END);
+  push_chunk(SAMPLED_CHUNKS);
   const uint32_t c0 = B[7].z, c1 = B[7].w;
   // tail chunk 56: the last 8 content bytes (the carry), one 8-byte block
   {
@@ -341,144 +278,10 @@ constexpr int PACKED_DEPTH = 6;
 constexpr int PACKED_LDS_DEPTH = PACKED_DEPTH - 1;
 constexpr int PACKED_BLOCK = 256;
 
-struct PackedStack {
-  uint32_t (*s)[8][PACKED_BLOCK];
-  uint32_t t;
-  uint32_t sp = 0;
-  uint32_t bottom[8];
-  __device__ __forceinline__ void push(const uint32_t (&cv)[8]) {
-    if (sp == 0) {
-#pragma unroll
-      for (int w = 0; w < 8; ++w) bottom[w] = cv[w];
-    } else {
-#pragma unroll
-      for (int w = 0; w < 8; ++w) s[sp - 1][w][t] = cv[w];
-    }
-    ++sp;
-  }
-  __device__ __forceinline__ void pop(uint32_t (&out)[8]) {
-    --sp;
-    if (sp == 0) {
-#pragma unroll
-      for (int w = 0; w < 8; ++w) out[w] = bottom[w];
-    } else {
-#pragma unroll
-      for (int w = 0; w < 8; ++w) out[w] = s[sp - 1][w][t];
-    }
-  }
-};
-
-// Always 8 x 16-B loads: a quad past the content is re-pointed at quad 0 (in bounds; an
-// empty content still has 16 readable bytes, see the ABI) instead of being predicated off
-// — a `cond ? q[i] : 0` load is lowered to four dword loads per quad.  Its garbage can
-// only reach the message's final block, which mask_tail() zeroes past the end.
-__device__ __forceinline__ void load_pair_pred(const uint4* __restrict__ q, uint32_t P,
-                                               uint32_t clen, uint4 (&buf)[8]) {
-  const uint32_t b0 = P << 7;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) buf[i] = q[(b0 + 16u * i < clen) ? 8u * P + i : 0u];
-}
-
-__device__ __forceinline__ void mask_tail(uint32_t (&m)[16], uint32_t blen) {
-#pragma unroll
-  for (int w = 0; w < 16; ++w) {
-    const int vb = (int)blen - 4 * w;
-    m[w] &= vb >= 4 ? 0xFFFFFFFFu : (vb <= 0 ? 0u : ((1u << (8 * vb)) - 1u));
-  }
-}
-
-// One FULL 1 KiB chunk (not the message's last) of a K2 lane: 16 blocks of 64 B with the
-// chunk flags on blocks 0 and 15 — none of the generic loop's per-block length, mask and
-// flag logic, and unclamped loads for the chunk's own pairs (a full chunk's content quads
-// are readable: clen > 1024c + 1016 puts its 16-B round-up past the chunk).  Only the
-// prefetch of the next chunk's first pair is clamped.  A holds pair 8c on entry and pair
-// 8(c+1) on exit.  Lanes of a wave share the chunk count (the visiting order is sorted on
-// it), so this loop is wave-uniform.
-__device__ __forceinline__ void packed_full_chunk(const uint4* __restrict__ q, uint32_t clen,
-                                                  uint32_t c, uint32_t (&cv)[8], uint4 (&A)[8],
-                                                  uint4 (&B)[8], uint32_t& c0, uint32_t& c1) {
-  set_iv(cv);
-  // K1's ping-pong schedule (no register moves): pairs 0..5 in the loop, 6 and 7 peeled so
-  // that the clamped prefetch of the next chunk's first pair does not merge with the
-  // unclamped loads into per-dword select loads (that merge measured 2.8x slower)
-#pragma unroll 1
-  for (uint32_t pp = 0; pp < 3; ++pp) {
-    const uint32_t P = 8u * c + 2u * pp;
-    load_pair(q, P + 1, B);
-    compress_pair(cv, A, c0, c1, c, pp == 0 ? (uint32_t)CHUNK_START : 0u, 0u);
-    load_pair(q, P + 2, A);
-    compress_pair(cv, B, c0, c1, c, 0u, 0u);
-  }
-  load_pair(q, 8u * c + 7u, B);
-  compress_pair(cv, A, c0, c1, c, 0u, 0u);
-  load_pair_pred(q, 8u * c + 8u, clen, A);
-  compress_pair(cv, B, c0, c1, c, 0u, CHUNK_END);
-}
-
-__device__ __forceinline__ uint64_t cas_lane_packed(const uint4* __restrict__ q, uint32_t clen,
-                                                    uint64_t size,
-                                                    PackedStack& stk) {
-  const uint32_t mlen = clen + 8u;
-  const uint32_t nblocks = (mlen + 63u) >> 6;   // >= 1
-  const uint32_t nchunks = (mlen + 1023u) >> 10;
-  const uint32_t npairs = (nblocks + 1u) >> 1;
-  uint32_t c0 = (uint32_t)size, c1 = (uint32_t)(size >> 32);
-  uint4 A[8], B[8];
-  load_pair_pred(q, 0, clen, A);
-  uint32_t cv[8];
-  for (uint32_t c = 0; c + 1 < nchunks; ++c) {
-    packed_full_chunk(q, clen, c, cv, A, B, c0, c1);
-    uint32_t total = c + 1;
-    while ((total & 1u) == 0u) {
-      uint32_t left[8];
-      stk.pop(left);
-      parent(cv, left, cv, 0u);
-      total >>= 1;
-    }
-    stk.push(cv);
-  }
-  {
-    // the message's last chunk: generic blocks with length, tail mask and ROOT flags
-    const uint32_t c = nchunks - 1;
-    const uint32_t cblocks = nblocks - 16u * c;
-    set_iv(cv);
-    for (uint32_t b = 0; b < cblocks; b += 2) {
-      const uint32_t P = 8u * c + (b >> 1);
-      if (P + 1 < npairs) load_pair_pred(q, P + 1, clen, B);
-      const uint32_t j = 16u * c + b;  // global block index of the pair's first block
-      const bool root1 = c == 0;
-      {
-        uint32_t m[16] = {c0, c1, A[0].x, A[0].y, A[0].z, A[0].w, A[1].x, A[1].y,
-                          A[1].z, A[1].w, A[2].x, A[2].y, A[2].z, A[2].w, A[3].x, A[3].y};
-        const uint32_t rem = mlen - (j << 6), blen = rem < 64u ? rem : 64u;
-        if (blen < 64u) mask_tail(m, blen);
-        const bool end = (b + 1 == cblocks);
-        const uint32_t f = (b == 0 ? (uint32_t)CHUNK_START : 0u) | (end ? (uint32_t)CHUNK_END : 0u) |
-                           (end && root1 ? (uint32_t)ROOT : 0u);
-        compress(cv, m, c, 0u, blen, f);
-      }
-      if (b + 1 < cblocks) {
-        uint32_t m[16] = {A[3].z, A[3].w, A[4].x, A[4].y, A[4].z, A[4].w, A[5].x, A[5].y,
-                          A[5].z, A[5].w, A[6].x, A[6].y, A[6].z, A[6].w, A[7].x, A[7].y};
-        const uint32_t rem = mlen - ((j + 1) << 6), blen = rem < 64u ? rem : 64u;
-        if (blen < 64u) mask_tail(m, blen);
-        const bool end = (b + 2 == cblocks);
-        const uint32_t f = (end ? (uint32_t)CHUNK_END : 0u) | (end && root1 ? (uint32_t)ROOT : 0u);
-        compress(cv, m, c, 0u, blen, f);
-      }
-      c0 = A[7].z;
-      c1 = A[7].w;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) A[i] = B[i];
-    }
-  }
-  while (stk.sp > 0) {
-    uint32_t left[8];
-    stk.pop(left);
-    parent(cv, left, cv, stk.sp == 0 ? (uint32_t)ROOT : 0u);
-  }
-  return key_of(cv);
-}
+// The lane program is blake3_lane.hpp's lane_message<PREFIXED>: full chunks on the fixed
+// 16-block schedule, only the last chunk generic.  Lanes of a wave share the chunk count (the
+// visiting order is sorted on it), so the full-chunk loop is wave-uniform.
+using PackedStack = CvStack<PACKED_BLOCK, true>;
 
 // ---- K1L: chunk-parallel latency path (small batches) ---------------------------------
 // A file per wave (a lane per 1 KiB chunk) or per 16-lane segment (4+ chunks per lane),
@@ -493,9 +296,8 @@ constexpr int CP_MAX_CHUNKS = 104;
 // CV of chunk c of M = le64(size) || content[0, clen); ROOT when M is a single chunk.
 __device__ __forceinline__ void cas_chunk_cv(const uint4* __restrict__ q, uint32_t clen,
                                              uint64_t size, uint32_t c, uint32_t (&cv)[8]) {
-  const uint32_t mlen = clen + 8u;
-  const uint32_t nblocks = (mlen + 63u) >> 6;
-  const uint32_t nchunks = (mlen + 1023u) >> 10;
+  const uint32_t nblocks = (clen + 8u + 63u) >> 6;
+  const uint32_t nchunks = (clen + 8u + 1023u) >> 10;
   const bool last = (c + 1 == nchunks);
   const bool root = last && c == 0;
   const uint32_t cblocks = last ? (nblocks - 16u * c) : 16u;
@@ -507,36 +309,8 @@ __device__ __forceinline__ void cas_chunk_cv(const uint4* __restrict__ q, uint32
     c1 = p.w;
   }
   uint4 A[8], B[8];
-  load_pair_pred(q, 8u * c, clen, A);
-  set_iv(cv);
-  for (uint32_t b = 0; b < cblocks; b += 2) {
-    const uint32_t P = 8u * c + (b >> 1);
-    if (b + 2 < cblocks) load_pair_pred(q, P + 1, clen, B);
-    const uint32_t j = 16u * c + b;
-    {
-      uint32_t m[16] = {c0, c1, A[0].x, A[0].y, A[0].z, A[0].w, A[1].x, A[1].y,
-                        A[1].z, A[1].w, A[2].x, A[2].y, A[2].z, A[2].w, A[3].x, A[3].y};
-      const uint32_t rem = mlen - (j << 6), blen = rem < 64u ? rem : 64u;
-      if (blen < 64u) mask_tail(m, blen);
-      const bool end = (b + 1 == cblocks);
-      const uint32_t f = (b == 0 ? (uint32_t)CHUNK_START : 0u) | (end ? (uint32_t)CHUNK_END : 0u) |
-                         (end && root ? (uint32_t)ROOT : 0u);
-      compress(cv, m, c, 0u, blen, f);
-    }
-    if (b + 1 < cblocks) {
-      uint32_t m[16] = {A[3].z, A[3].w, A[4].x, A[4].y, A[4].z, A[4].w, A[5].x, A[5].y,
-                        A[5].z, A[5].w, A[6].x, A[6].y, A[6].z, A[6].w, A[7].x, A[7].y};
-      const uint32_t rem = mlen - ((j + 1) << 6), blen = rem < 64u ? rem : 64u;
-      if (blen < 64u) mask_tail(m, blen);
-      const bool end = (b + 2 == cblocks);
-      const uint32_t f = (end ? (uint32_t)CHUNK_END : 0u) | (end && root ? (uint32_t)ROOT : 0u);
-      compress(cv, m, c, 0u, blen, f);
-    }
-    c0 = A[7].z;
-    c1 = A[7].w;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) A[i] = B[i];
-  }
+  line_clamped(q, 8u * c, clen, A);
+  last_chunk<PREFIXED>(q, clen, c, cblocks, root, cv, A, B, c0, c1);
 }
 
 // K1L: a file per SEG-lane segment (64/SEG files per wave).  Segment lane l hashes the
@@ -559,7 +333,7 @@ __device__ __forceinline__ void chunkpar_wave(const uint8_t* __restrict__ arena,
                                               const uint64_t* __restrict__ sizes, uint64_t n,
                                               const uint32_t* __restrict__ order,
                                               uint64_t* __restrict__ keys) {
-  __shared__ uint32_t stk[CP_DEPTH][8][64];  // word-major per-lane columns: conflict-free
+  __shared__ uint32_t stack_lds[CP_DEPTH][8][64];
   const uint32_t lane = threadIdx.x;
   const uint32_t sl = lane % SEG;
   const uint64_t slot = (uint64_t)blockIdx.x * (64 / SEG) + lane / SEG;
@@ -580,34 +354,15 @@ __device__ __forceinline__ void chunkpar_wave(const uint8_t* __restrict__ arena,
   const uint32_t c0 = ok ? sl * cpl : 0u;
   const uint32_t c1 = ok ? min(nchunks, c0 + cpl) : 0u;
   uint32_t cv[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-  uint32_t sp = 0;
+  CvStack<64, false> stk{stack_lds, lane};
   for (uint32_t c = c0; c < c1; ++c) {
     cas_chunk_cv(q, clen, size, c, cv);  // ROOT already set for a one-chunk message
-    uint32_t total = c - c0 + 1u;
-    while ((total & 1u) == 0u) {
-      uint32_t l[8];
-      --sp;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) l[w] = stk[sp][w][lane];
-      parent(cv, l, cv, (whole && c + 1u == nchunks && sp == 0u) ? (uint32_t)ROOT : 0u);
-      total >>= 1;
-    }
-#pragma unroll
-    for (int w = 0; w < 8; ++w) stk[sp][w][lane] = cv[w];
-    ++sp;
+    merge_push(stk, cv, c - c0 + 1u, (whole && c + 1u == nchunks) ? (uint32_t)ROOT : 0u);
   }
   // a partial (last) group: merge its pending subtrees right to left
-  if (sp > 0u) {
-    --sp;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) cv[w] = stk[sp][w][lane];
-    while (sp > 0u) {
-      uint32_t l[8];
-      --sp;
-#pragma unroll
-      for (int w = 0; w < 8; ++w) l[w] = stk[sp][w][lane];
-      parent(cv, l, cv, (whole && sp == 0u) ? (uint32_t)ROOT : 0u);
-    }
+  if (stk.sp > 0u) {
+    stk.pop(cv);
+    fold(stk, cv, whole ? (uint32_t)ROOT : 0u);
   }
   uint32_t count = whole ? 1u : (nchunks + cpl - 1u) / cpl;  // lane subtrees of this file
   segment_merge<SEG, 1u>(cv, sl, count);
@@ -639,7 +394,9 @@ sd_cas_packed_kernel(const uint8_t* __restrict__ arena, const uint64_t* __restri
   const uint32_t f = order ? order[t] : (uint32_t)t;
   const uint4* q = reinterpret_cast<const uint4*>(arena + offs[f]);
   PackedStack stk{stack_lds, threadIdx.x};
-  keys[f] = cas_lane_packed(q, lens[f], sizes[f], stk);
+  uint32_t cv[8];
+  lane_message<PREFIXED>(q, lens[f], sizes[f], stk, cv);
+  keys[f] = key_of(cv);
 }
 
 }  // namespace sdcas

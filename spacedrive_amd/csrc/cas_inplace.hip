@@ -22,7 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "blake3_device.hpp"
+#include "blake3_lane.hpp"
 #include "sd_debug.h"
 #include "sd_inplace_plan.h"
 #include "sd_kernels.h"
@@ -138,8 +138,8 @@ sd_cas_inplace_kernel(const uint8_t* __restrict__ arena, const uint64_t* __restr
   for (uint32_t pp = 0; pp < 4; ++pp) {
     load_line_shifted(w, 2u * pp + 1u, sh, pp < 3, B);
     {  // line 2pp: the chunk's first block carries CHUNK_START, and is all of the tail chunk
-      uint32_t m[16] = {c0, c1, A[0].x, A[0].y, A[0].z, A[0].w, A[1].x, A[1].y,
-                        A[1].z, A[1].w, A[2].x, A[2].y, A[2].z, A[2].w, A[3].x, A[3].y};
+      uint32_t m[16];
+      words_lo<PREFIXED>(m, A, c0, c1);
       uint32_t blen = BLOCK_LEN, fl = pp == 0 ? (uint32_t)CHUNK_START : 0u;
       if (pp == 0 && tail) {
 #pragma unroll
@@ -152,23 +152,13 @@ sd_cas_inplace_kernel(const uint8_t* __restrict__ arena, const uint64_t* __restr
 #pragma unroll
         for (int k = 0; k < 8; ++k) first[k] = cv[k];
       }
-      const uint32_t m2[16] = {A[3].z, A[3].w, A[4].x, A[4].y, A[4].z, A[4].w, A[5].x, A[5].y,
-                               A[5].z, A[5].w, A[6].x, A[6].y, A[6].z, A[6].w, A[7].x, A[7].y};
-      compress(cv, m2, c, 0u, BLOCK_LEN, 0u);
+      compress_hi<PREFIXED>(cv, A, c, 0u);
       c0 = A[7].z;
       c1 = A[7].w;
     }
     if (pp < 3) load_line_shifted(w, 2u * pp + 2u, sh, true, A);
-    {  // line 2pp + 1: CHUNK_END on the chunk's 16th block
-      const uint32_t m[16] = {c0, c1, B[0].x, B[0].y, B[0].z, B[0].w, B[1].x, B[1].y,
-                              B[1].z, B[1].w, B[2].x, B[2].y, B[2].z, B[2].w, B[3].x, B[3].y};
-      compress(cv, m, c, 0u, BLOCK_LEN, 0u);
-      const uint32_t m2[16] = {B[3].z, B[3].w, B[4].x, B[4].y, B[4].z, B[4].w, B[5].x, B[5].y,
-                               B[5].z, B[5].w, B[6].x, B[6].y, B[6].z, B[6].w, B[7].x, B[7].y};
-      compress(cv, m2, c, 0u, BLOCK_LEN, pp == 3 ? (uint32_t)CHUNK_END : 0u);
-      c0 = B[7].z;
-      c1 = B[7].w;
-    }
+    // line 2pp + 1: CHUNK_END on the chunk's 16th block
+    compress_line<PREFIXED>(cv, B, c0, c1, c, 0u, pp == 3 ? (uint32_t)CHUNK_END : 0u);
   }
   if (tail) {
 #pragma unroll

@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "blake3_device.hpp"
+#include "blake3_lane.hpp"
 #include "sd_checksum.h"
 #include "sd_debug.h"
 #include "sd_group.h"
@@ -33,6 +33,14 @@ constexpr int GROUP = 256;  // threads per workgroup = CVs per reduce workgroup
 constexpr uint64_t GROUP_CHUNKS = (uint64_t)GROUP * K3_LANE_CHUNKS;  // chunks per subtree
 static_assert((K3_LANE_CHUNKS & (K3_LANE_CHUNKS - 1)) == 0, "subtrees must be 2^k chunks");
 
+// A full block of line A (its low or its high one) under the file path's 64-bit chunk counter.
+template <bool HI>
+__device__ __forceinline__ void compress64(uint32_t (&cv)[8], const uint4 (&A)[8], uint64_t ctr, uint32_t f) {
+  uint32_t m[16];
+  if (HI) words_hi<PLAIN>(m, A); else words_lo<PLAIN>(m, A);
+  compress(cv, m, (uint32_t)ctr, (uint32_t)(ctr >> 32), BLOCK_LEN, f);
+}
+
 // CV of one FULL 1 KiB chunk (never a root: a one-chunk input takes chunk_cv below), with
 // the chunk's first line pair already in A (loaded one chunk ahead), and the
 // first pair of the lane's NEXT chunk (`next`, when non-null) loaded into A during this
@@ -47,33 +55,16 @@ __device__ __forceinline__ void full_chunk_cv_pf(const uint4* __restrict__ q, co
   for (uint32_t p = 0; p < 8; p += 2) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) B[i] = q[8u * (p + 1) + i];
-    {
-      const uint32_t m[16] = {A[0].x, A[0].y, A[0].z, A[0].w, A[1].x, A[1].y, A[1].z, A[1].w,
-                              A[2].x, A[2].y, A[2].z, A[2].w, A[3].x, A[3].y, A[3].z, A[3].w};
-      compress(cv, m, (uint32_t)ctr, (uint32_t)(ctr >> 32), BLOCK_LEN, p == 0 ? (uint32_t)CHUNK_START : 0u);
-    }
-    {
-      const uint32_t m[16] = {A[4].x, A[4].y, A[4].z, A[4].w, A[5].x, A[5].y, A[5].z, A[5].w,
-                              A[6].x, A[6].y, A[6].z, A[6].w, A[7].x, A[7].y, A[7].z, A[7].w};
-      compress(cv, m, (uint32_t)ctr, (uint32_t)(ctr >> 32), BLOCK_LEN, 0u);
-    }
+    compress64<false>(cv, A, ctr, p == 0 ? (uint32_t)CHUNK_START : 0u);
+    compress64<true>(cv, A, ctr, 0u);
     // the next pair of this chunk, or the first pair of the lane's next chunk
     const uint4* src = p + 2 < 8 ? q + 8u * (p + 2) : next;
     if (src) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) A[i] = src[i];
     }
-    {
-      const uint32_t m[16] = {B[0].x, B[0].y, B[0].z, B[0].w, B[1].x, B[1].y, B[1].z, B[1].w,
-                              B[2].x, B[2].y, B[2].z, B[2].w, B[3].x, B[3].y, B[3].z, B[3].w};
-      compress(cv, m, (uint32_t)ctr, (uint32_t)(ctr >> 32), BLOCK_LEN, 0u);
-    }
-    {
-      const uint32_t m[16] = {B[4].x, B[4].y, B[4].z, B[4].w, B[5].x, B[5].y, B[5].z, B[5].w,
-                              B[6].x, B[6].y, B[6].z, B[6].w, B[7].x, B[7].y, B[7].z, B[7].w};
-      compress(cv, m, (uint32_t)ctr, (uint32_t)(ctr >> 32), BLOCK_LEN,
-               p == 6 ? (uint32_t)CHUNK_END : 0u);
-    }
+    compress64<false>(cv, B, ctr, 0u);
+    compress64<true>(cv, B, ctr, p == 6 ? (uint32_t)CHUNK_END : 0u);
   }
 }
 
@@ -95,17 +86,11 @@ __device__ __forceinline__ void chunk_cv(const uint4* __restrict__ q, uint32_t c
   };
   if (clen) load(0);
   for (uint32_t b = 0; b < nblk; ++b) {
-    uint32_t m[16] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w,
-                      a2.x, a2.y, a2.z, a2.w, a3.x, a3.y, a3.z, a3.w};
+    uint32_t m[16];
+    quads_to_words(m, a0, a1, a2, a3);
     const uint32_t rem = clen - (b << 6);
     const uint32_t blen = clen == 0 ? 0u : (rem < 64u ? rem : 64u);
-    if (blen < 64u) {
-#pragma unroll
-      for (int w = 0; w < 16; ++w) {
-        const int vb = (int)blen - 4 * w;
-        m[w] &= vb >= 4 ? 0xFFFFFFFFu : (vb <= 0 ? 0u : ((1u << (8 * vb)) - 1u));
-      }
-    }
+    if (blen < 64u) mask_tail(m, blen);
     if (b + 1 < nblk) load(b + 1);
     uint32_t flags = (b == 0 ? (uint32_t)CHUNK_START : 0u) | (b + 1 == nblk ? (uint32_t)CHUNK_END : 0u);
     if (root && b + 1 == nblk) flags |= ROOT;
@@ -573,140 +558,6 @@ constexpr uint64_t LANE_BLOCK_KEY_MEAN = 16384;
 constexpr int LANE_KEY_BITS_BLOCKS = ilog2c(MID_CHUNKS * 16) + 1;  // 0..4,096: 13 bits
 constexpr int LANE_KEY_BITS_CHUNKS = ilog2c(MID_CHUNKS) + 1;       // 0..256: 9 bits
 
-struct LaneStack {
-  uint32_t (*s)[8][LANE_BLOCK];
-  uint32_t t;
-  uint32_t sp = 0;
-  uint32_t bottom[8];
-  __device__ __forceinline__ void push(const uint32_t (&cv)[8]) {
-    if (sp == 0) {
-#pragma unroll
-      for (int w = 0; w < 8; ++w) bottom[w] = cv[w];
-    } else {
-#pragma unroll
-      for (int w = 0; w < 8; ++w) s[sp - 1][w][t] = cv[w];
-    }
-    ++sp;
-  }
-  __device__ __forceinline__ void pop(uint32_t (&out)[8]) {
-    --sp;
-    if (sp == 0) {
-#pragma unroll
-      for (int w = 0; w < 8; ++w) out[w] = bottom[w];
-    } else {
-#pragma unroll
-      for (int w = 0; w < 8; ++w) out[w] = s[sp - 1][w][t];
-    }
-  }
-};
-
-// line P of the buffer (quads 8P..8P+7); all 8 quads are in bounds
-__device__ __forceinline__ void lane_line(const uint4* __restrict__ q, uint32_t P, uint4 (&buf)[8]) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) buf[i] = q[8u * P + i];
-}
-// the same with quads at or past the 16-B round-up of len re-pointed at quad 0 (len > 0);
-// their bytes only reach the final block, which is masked
-__device__ __forceinline__ void lane_line_clamped(const uint4* __restrict__ q, uint32_t P,
-                                                  uint32_t len, uint4 (&buf)[8]) {
-  const uint32_t b0 = P << 7;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) buf[i] = q[(b0 + 16u * i < len) ? 8u * P + i : 0u];
-}
-__device__ __forceinline__ void lane_compress_line(uint32_t (&cv)[8], const uint4 (&A)[8],
-                                                   uint32_t ctr, uint32_t f0, uint32_t f1) {
-  {
-    const uint32_t m[16] = {A[0].x, A[0].y, A[0].z, A[0].w, A[1].x, A[1].y, A[1].z, A[1].w,
-                            A[2].x, A[2].y, A[2].z, A[2].w, A[3].x, A[3].y, A[3].z, A[3].w};
-    compress(cv, m, ctr, 0u, BLOCK_LEN, f0);
-  }
-  {
-    const uint32_t m[16] = {A[4].x, A[4].y, A[4].z, A[4].w, A[5].x, A[5].y, A[5].z, A[5].w,
-                            A[6].x, A[6].y, A[6].z, A[6].w, A[7].x, A[7].y, A[7].z, A[7].w};
-    compress(cv, m, ctr, 0u, BLOCK_LEN, f1);
-  }
-}
-
-// CV of full chunk c (not the buffer's last): A holds line 8c on entry and line 8(c+1)
-// (clamped: the next chunk may be the partial last one) on exit; the lines ping-pong
-// between A and B with no register moves.
-__device__ __forceinline__ void lane_full_chunk(const uint4* __restrict__ q, uint32_t len, uint32_t c,
-                                                uint32_t (&cv)[8], uint4 (&A)[8], uint4 (&B)[8]) {
-  set_iv(cv);
-#pragma unroll 1
-  for (uint32_t pp = 0; pp < 3; ++pp) {
-    const uint32_t P = 8u * c + 2u * pp;
-    lane_line(q, P + 1, B);
-    lane_compress_line(cv, A, c, pp == 0 ? (uint32_t)CHUNK_START : 0u, 0u);
-    lane_line(q, P + 2, A);
-    lane_compress_line(cv, B, c, 0u, 0u);
-  }
-  lane_line(q, 8u * c + 7u, B);
-  lane_compress_line(cv, A, c, 0u, 0u);
-  lane_line_clamped(q, 8u * c + 8u, len, A);
-  lane_compress_line(cv, B, c, 0u, CHUNK_END);
-}
-
-// BLAKE3 digest of buffer q[0, len), len <= LANE_CHUNKS KiB, into cv
-__device__ __forceinline__ void lane_digest(const uint4* __restrict__ q, uint32_t len, LaneStack& stk,
-                                            uint32_t (&cv)[8]) {
-  const uint32_t nch = len == 0 ? 1u : (len + 1023u) >> 10;
-  uint4 A[8], B[8];
-  if (len) {
-    lane_line_clamped(q, 0, len, A);
-  } else {  // an empty buffer reads nothing (its round-up is 0 bytes)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) A[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
-  for (uint32_t c = 0; c + 1 < nch; ++c) {
-    lane_full_chunk(q, len, c, cv, A, B);
-    for (uint32_t total = c + 1; (total & 1u) == 0u; total >>= 1) {
-      uint32_t left[8];
-      stk.pop(left);
-      parent(cv, left, cv, 0u);
-    }
-    stk.push(cv);
-  }
-  // the last chunk: per-block length, tail mask, CHUNK_END and (single chunk) ROOT
-  const uint32_t c = nch - 1;
-  const uint32_t clen = len - (c << 10);
-  const uint32_t cblocks = clen == 0 ? 1u : (clen + 63u) >> 6;
-  set_iv(cv);
-  for (uint32_t b = 0; b < cblocks; b += 2) {
-    if (b + 2 < cblocks) lane_line_clamped(q, 8u * c + (b >> 1) + 1u, len, B);
-#pragma unroll
-    for (uint32_t h = 0; h < 2; ++h) {
-      if (h == 1 && b + 1 >= cblocks) break;
-      uint32_t m[16];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const uint4 v = A[4 * h + i];
-        m[4 * i] = v.x; m[4 * i + 1] = v.y; m[4 * i + 2] = v.z; m[4 * i + 3] = v.w;
-      }
-      const uint32_t bo = (b + h) << 6;
-      const uint32_t blen = clen - bo < 64u ? clen - bo : 64u;  // clen > bo, or both 0
-      if (blen < 64u) {
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-          const int vb = (int)blen - 4 * w;
-          m[w] &= vb >= 4 ? 0xFFFFFFFFu : (vb <= 0 ? 0u : ((1u << (8 * vb)) - 1u));
-        }
-      }
-      const bool end = b + h + 1 == cblocks;
-      const uint32_t f = (b + h == 0 ? (uint32_t)CHUNK_START : 0u) | (end ? (uint32_t)CHUNK_END : 0u) |
-                         (end && nch == 1 ? (uint32_t)ROOT : 0u);
-      compress(cv, m, c, 0u, blen, f);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) A[i] = B[i];
-  }
-  while (stk.sp > 0) {
-    uint32_t left[8];
-    stk.pop(left);
-    parent(cv, left, cv, stk.sp == 0 ? (uint32_t)ROOT : 0u);
-  }
-}
-
 // visiting key: descending chunk count up to MID_CHUNKS, MID_CHUNKS (last) for the rest;
 // info[0] += the lane class's chunks, info[1..3] += the 65..256 / 17..64 / <= 16 chunk
 // class sizes (wave sums, one atomic each per wave)
@@ -763,9 +614,9 @@ sd_b3_batch_lane(const uint8_t* __restrict__ arena, uint64_t arena_bytes,
   const uint32_t f = order[t];
   const uint64_t len = lens[f];
   if (chunks_of(len) > lane_cut(lane_info) || !buffer_ok(offs[f], len, arena_bytes)) return;
-  LaneStack stk{stack_lds, threadIdx.x};
+  CvStack<LANE_BLOCK, true> stk{stack_lds, threadIdx.x};
   uint32_t cv[8];
-  lane_digest(reinterpret_cast<const uint4*>(arena + offs[f]), (uint32_t)len, stk, cv);
+  lane_message<PLAIN>(reinterpret_cast<const uint4*>(arena + offs[f]), (uint32_t)len, 0ull, stk, cv);
 #pragma unroll
   for (int k = 0; k < 8; ++k) digests[8ull * f + k] = cv[k];
 }

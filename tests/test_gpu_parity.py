@@ -109,6 +109,29 @@ def test_packed_kernel_edges_vs_oracle(path_eng, oracle):
     assert not bad, bad[:10]
 
 
+def test_packed_chunk_count_sweep(path_eng, oracle):
+    """Every chunk count of the whole-file path, 1..104, with the message ending one byte
+    before, at, and one byte past the chunk boundary: every depth of K2's CV stack and every
+    fold, and K1L at 1-2 chunks per lane (a file per wave) and 1-8 (a file per 16-lane segment).
+    The padding is 0xFF.  (tests/test_lane_walker_cpu.py walks the same list on the CPU.)"""
+    from spacedrive_amd.cas import MAX_PACKED_CONTENT_LEN
+    eng = path_eng
+    rng = np.random.default_rng(12)
+    lens = [min(max(k * 1024 - 8 + d, 0), MAX_PACKED_CONTENT_LEN) for k in range(1, 105) for d in (-1, 0, 1)]
+    contents = [rng.integers(0, 256, L, dtype=np.uint8).tobytes() for L in lens]
+    arena, offs = packed_arena(contents)
+    for c, off in zip(contents, offs):
+        arena[off + len(c): off + (len(c) + 15) // 16 * 16] = 0xFF
+    sizes = np.array([L if L % 3 else L * 3 + (1 << 33) + 200_000 for L in lens], dtype=np.uint64)
+    want = oracle.cas_keys(arena, offs, np.array(lens, dtype=np.uint64), sizes)
+    keys = torch.zeros(len(lens), dtype=torch.int64, device="cuda")
+    eng.hash_packed(torch.from_numpy(arena).cuda(), dev64(offs),
+                    torch.tensor(lens, dtype=torch.int32, device="cuda"), dev64(sizes), keys)
+    got = host64(keys)
+    bad = [(lens[i], f"{got[i]:016x}", f"{want[i]:016x}") for i in range(len(lens)) if got[i] != want[i]]
+    assert not bad, bad[:10]
+
+
 def test_host_generate_cas_ids_mixed(path_eng, oracle, golden):
     eng = path_eng
     g = golden["cas"]

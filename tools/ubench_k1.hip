@@ -59,8 +59,8 @@ __device__ __forceinline__ uint64_t cas_lane_sampled(const uint4* __restrict__ q
       const uint32_t P = 8u * c + 2u * pp;
       load_pair<NT, L>(q, P, A);
       load_pair<NT, L>(q, P + 1, B);
-      compress_pair(cv, A, c0, c1, c, pp == 0 ? (uint32_t)CHUNK_START : 0u, 0u);
-      compress_pair(cv, B, c0, c1, c, 0u, pp == 3 ? (uint32_t)CHUNK_END : 0u);
+      compress_line<PREFIXED>(cv, A, c0, c1, c, pp == 0 ? (uint32_t)CHUNK_START : 0u, 0u);
+      compress_line<PREFIXED>(cv, B, c0, c1, c, 0u, pp == 3 ? (uint32_t)CHUNK_END : 0u);
     }
     uint32_t total = c + 1;
     while ((total & 1u) == 0u) {
