@@ -24,9 +24,9 @@
 #include <stdint.h>
 
 #include "blake3_lane.hpp"
+#include "blake3_tree.hpp"
 #include "sd_kernels.h"
 #include "sd_mix.h"
-#include "sd_segment_merge.h"
 
 namespace sdcas {
 
@@ -286,7 +286,7 @@ using PackedStack = CvStack<PACKED_BLOCK, true>;
 // ---- K1L: chunk-parallel latency path (small batches) ---------------------------------
 // A file per wave (a lane per 1 KiB chunk) or per 16-lane segment (4+ chunks per lane),
 // then a level-wise pair-and-promote merge of the lanes' subtree CVs across lanes (DPP row
-// shifts inside a 16-lane row).  A file's latency is ~16 + log2(chunks) compression times
+// shifts inside a 16-lane row: segment_merge, blake3_tree.hpp).  A file's latency is ~16 + log2(chunks) compression times
 // instead of the lane-per-file kernels' 953, at ~68 % (wave per file) / ~84 % (4 files per
 // wave) lane efficiency — the right trade when a batch is too small to fill the chip (the
 // reference's job step is 100 files, file_identifier/mod.rs:34).  Chosen by the host below

@@ -14,19 +14,19 @@
 //   K1P       K1L's wave-per-file shape: lane c hashes chunk c of the 57-chunk message
 //             M = le64(len) || header || 4 samples || footer, reading its 1,016 body bytes and
 //             its 8 carry bytes where they lie in the file (sd_inplace_plan.h), and the lanes'
-//             CVs merge across lanes with segment_merge.  Sample and footer offsets have any
-//             byte alignment (k*j and len are arbitrary), so a lane loads 4-B aligned dwords
-//             (dwordx4 runs plus one dword per 128-B line) and realigns them in registers
+//             CVs merge across lanes with segment_merge (blake3_tree.hpp).  Sample and footer
+//             offsets have any byte alignment (k*j and len are arbitrary), so a lane loads 4-B
+//             aligned dwords (dwordx4 runs plus one per 128-B line) and realigns them in registers
 //             with v_alignbyte_b32 by its own byte shift: ~256 alignbytes on top of a chunk's
 //             ~10,900 VALU instructions.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "blake3_lane.hpp"
+#include "blake3_tree.hpp"
 #include "sd_debug.h"
 #include "sd_inplace_plan.h"
 #include "sd_kernels.h"
-#include "sd_segment_merge.h"
 #include "sd_ws.h"
 
 namespace sdcas {

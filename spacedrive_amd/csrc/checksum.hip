@@ -12,11 +12,13 @@
 //   sd_b3_reduce_cvs: the same pair-and-promote over 256 CVs at a time, repeated until
 //     one CV remains; only the very last parent carries ROOT.
 // Level-wise pair-and-promote over aligned groups of 2^k equals BLAKE3's left-balanced
-// tree (checked by the oracle's third formulation, blake3_levelwise).
+// tree (the oracle's third formulation, blake3_levelwise).  Every reduction here is tree_reduce
+// (blake3_tree.hpp) over a scope: the 256-thread workgroup, a wave, or a 16-lane slice of one.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "blake3_lane.hpp"
+#include "blake3_tree.hpp"
 #include "sd_checksum.h"
 #include "sd_debug.h"
 #include "sd_group.h"
@@ -98,44 +100,6 @@ __device__ __forceinline__ void chunk_cv(const uint4* __restrict__ q, uint32_t c
   }
 }
 
-// Pair-and-promote `count` (<= PER * 256) CVs held in LDS cvs[][8] down to one (in cvs[0]).
-// `root_last`: the final parent carries ROOT (only when this is the whole tree's top).
-// Thread t computes the parents t, t+256, ... of a level; all reads of a level finish
-// before its writes (parent p overwrites slot p, which another thread's pair may read).
-template <int PER>
-__device__ __forceinline__ void lds_reduce(uint32_t (*cvs)[8], uint32_t count, bool root_last) {
-  const uint32_t t = threadIdx.x;
-  while (count > 1) {
-    const uint32_t pairs = count >> 1;
-    const bool odd = count & 1u;
-    uint32_t out[PER][8];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-      const uint32_t p = t + (uint32_t)k * GROUP;
-      if (p < pairs) {
-        uint32_t l[8], r[8];
-#pragma unroll
-        for (int w = 0; w < 8; ++w) { l[w] = cvs[2 * p][w]; r[w] = cvs[2 * p + 1][w]; }
-        parent(out[k], l, r, (root_last && count == 2) ? (uint32_t)ROOT : 0u);
-      } else if (odd && p == pairs) {
-#pragma unroll
-        for (int w = 0; w < 8; ++w) out[k][w] = cvs[count - 1][w];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-      const uint32_t p = t + (uint32_t)k * GROUP;
-      if (p < pairs || (odd && p == pairs)) {
-#pragma unroll
-        for (int w = 0; w < 8; ++w) cvs[p][w] = out[k][w];
-      }
-    }
-    __syncthreads();
-    count = pairs + (odd ? 1u : 0u);
-  }
-}
-
 // Chunks [g*GC, g*GC+GC) of the buffer (global chunk index chunk0 + ...) -> their subtree
 // CV in out8[0..8); when the buffer has one group and root_if_single_group, the ROOT digest
 // (a single chunk is then the root itself).  Called by the whole workgroup; leaves cvs free.
@@ -181,7 +145,7 @@ __device__ __forceinline__ void group_subtree(const uint8_t* __restrict__ data, 
     }
   }
   __syncthreads();
-  lds_reduce<(LC + 1) / 2>(cvs, count, whole_tree);
+  tree_reduce<Workgroup256, (LC + 1) / 2>(cvs, count, whole_tree);
   if (t < 8) out8[t] = cvs[0][t];
   __syncthreads();  // cvs[0] read before the caller's next group overwrites it
 }
@@ -215,7 +179,7 @@ sd_b3_reduce_cvs(const uint32_t* __restrict__ in, uint64_t cnt, uint32_t* __rest
     for (int w = 0; w < 8; ++w) cvs[t][w] = in[(first + t) * 8 + w];
   }
   __syncthreads();
-  lds_reduce<1>(cvs, count, root_if_single_group && cnt <= (uint64_t)GROUP);
+  tree_reduce<Workgroup256, 1>(cvs, count, root_if_single_group && cnt <= (uint64_t)GROUP);
   if (t < 8) out[(uint64_t)blockIdx.x * 8 + t] = cvs[0][t];
 }
 
@@ -334,17 +298,10 @@ sd_b3_batch_owner(const uint32_t* __restrict__ gstart, const unsigned long long*
   }
 }
 
-// wave-synchronous LDS phases of the small-buffer path (one wave per buffer: no workgroup
-// barrier, only ordering of this wave's own LDS accesses)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // One buffer per SEG-lane segment (SEG = 16: buffers of <= 16 chunks, 4 per wave; SEG = 64:
 // 17..64 chunks, one per wave): lane l of the segment hashes chunk l, and the segment
-// pair-and-promotes its chunk CVs in its own LDS slice, log2(SEG) fixed levels run by the
-// whole wave in step (segments whose tree is done idle through the rest).
+// pair-and-promotes its chunk CVs in its own LDS slice; the four 16-lane segments of a wave
+// run log2(16) levels in step (segments whose tree is done idle through the rest).
 template <uint32_t SEG>
 __device__ __forceinline__ void batch_small_body(const uint8_t* __restrict__ arena,
                                                  uint64_t arena_bytes,
@@ -386,30 +343,7 @@ __device__ __forceinline__ void batch_small_body(const uint8_t* __restrict__ are
       }
     }
     wave_sync();
-    uint32_t c = count;
-#pragma unroll 1
-    for (uint32_t lvl = 1; lvl < SEG; lvl <<= 1) {
-      const uint32_t pairs = c >> 1;
-      const bool odd = c & 1u;
-      const bool work = c > 1 && (sl < pairs || (odd && sl == pairs));
-      uint32_t out[8];
-      if (c > 1 && sl < pairs) {
-        uint32_t l[8], r[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { l[k] = mine[2 * sl][k]; r[k] = mine[2 * sl + 1][k]; }
-        parent(out, l, r, c == 2 ? (uint32_t)ROOT : 0u);
-      } else if (work) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) out[k] = mine[c - 1][k];
-      }
-      wave_sync();
-      if (work) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) mine[sl][k] = out[k];
-      }
-      wave_sync();
-      if (c > 1) c = pairs + (odd ? 1u : 0u);
-    }
+    tree_reduce<WaveSlice<SEG>, 1>(mine, count, true);
     if (count > 1 && sl < 8) digests[8 * f + sl] = mine[0][sl];
     wave_sync();  // mine[0] read before the next buffer's chunk CVs overwrite it
   }
@@ -495,28 +429,7 @@ sd_b3_batch_mid(const uint8_t* __restrict__ arena, uint64_t arena_bytes,
       for (int q = 0; q < 8; ++q) mine[lane][q] = acc[q];
     }
     wave_sync();
-#pragma unroll 1
-    for (uint32_t c = count; c > 1;) {
-      const uint32_t pairs = c >> 1;
-      const bool odd = c & 1u;
-      uint32_t out[8];
-      if (lane < pairs) {
-        uint32_t l[8], r[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { l[q] = mine[2 * lane][q]; r[q] = mine[2 * lane + 1][q]; }
-        parent(out, l, r, c == 2 ? (uint32_t)ROOT : 0u);
-      } else if (odd && lane == pairs) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) out[q] = mine[c - 1][q];
-      }
-      wave_sync();
-      if (lane < pairs || (odd && lane == pairs)) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) mine[lane][q] = out[q];
-      }
-      wave_sync();
-      c = pairs + (odd ? 1u : 0u);
-    }
+    tree_reduce<WaveSlice<64>, 1>(mine, count, true);
     if (lane < 8) digests[8 * f + lane] = mine[0][lane];
     wave_sync();
   }
@@ -683,7 +596,7 @@ sd_b3_batch_blocks(const uint32_t* __restrict__ gstart, const uint32_t* __restri
         for (int w = 0; w < 8; ++w) work[t][w] = blk[8 * t + w];
       }
       __syncthreads();
-      lds_reduce<1>(work, m, false);
+      tree_reduce<Workgroup256, 1>(work, m, false);
       if (t < 8) blk[t] = work[0][t];
       __syncthreads();
     }
@@ -726,7 +639,7 @@ sd_b3_batch_reduce(const uint32_t* __restrict__ gstart, const uint32_t* __restri
         for (int w = 0; w < 8; ++w) work[t][w] = in[8 * (uint64_t)t * stride + w];
       }
       __syncthreads();
-      lds_reduce<1>(work, m, true);
+      tree_reduce<Workgroup256, 1>(work, m, true);
       if (t < 8) digests[8 * f + t] = work[0][t];
       __syncthreads();
     }

@@ -1280,6 +1280,39 @@ def test_checksums_batch_dev_vs_oracle(eng, oracle):
     assert (out.cpu().numpy() == got).all()
 
 
+def test_checksums_batch_chunk_count_sweep(eng, oracle):
+    """Every count of every pair-and-promote reduction of the batch chain in one
+    sd_cas_checksums_dev call (fewer than 65,536 buffers: no lane path, every buffer goes
+    through a reducing kernel): k = 1..256 chunks ending 1 byte into, 1 byte short of and at
+    the last chunk's end (sd_b3_batch_small16, small64, and mid at 2 and 4 chunks per lane);
+    single-group buffers of 257..272 chunks and of every k <= 1,024 with k mod 32 in {0, 1, 31}
+    (the workgroup reduction at two parents per thread, odd carries at both); g = 2..9 groups
+    with one chunk in the last (sd_b3_batch_reduce); a 0-byte buffer.  Shuffled arena order,
+    every digest vs the oracle."""
+    rng = np.random.default_rng(17)
+    lens = [0] + [n for k in range(1, 257) for n in ((k - 1) * 1024 + 1, k * 1024 - 1, k * 1024)]
+    lens += [(k - 1) * 1024 + 1 for k in range(257, 1025) if k <= 272 or k % 32 in (0, 1, 31)]
+    lens += [(g - 1) * (1 << 20) + 1 for g in (2, 3, 4, 5, 7, 8, 9)]
+    assert len(lens) < 65536
+    offs = np.zeros(len(lens), dtype=np.uint64)
+    o = 0
+    for i in rng.permutation(len(lens)):  # arena order != index order
+        offs[i] = o
+        o += (lens[i] + 15) // 16 * 16 + 16 * int(rng.integers(0, 3))
+    arena_bytes = o + 16
+    arena = torch.empty(arena_bytes, dtype=torch.uint8, device="cuda")
+    eng.synth_stream(92, 1, 0, arena_bytes // 8 * 8, arena)
+    host = arena.cpu().numpy()
+    out = torch.zeros((len(lens), 32), dtype=torch.uint8, device="cuda")
+    eng.checksums_dev(arena, dev64(offs), dev64(np.array(lens, dtype=np.uint64)), out)
+    got = out.cpu().numpy()
+    bad = [(i, L) for i, L in enumerate(lens)
+           if got[i].tobytes() != oracle.blake3(host[int(offs[i]):int(offs[i]) + L].tobytes())]
+    assert not bad, (len(bad), bad[:8])
+    del arena
+    torch.cuda.empty_cache()
+
+
 @pytest.mark.parametrize("shape", ["uniform", "skewed"])
 def test_checksums_batch_lane_path(eng, oracle, shape):
     """A batch of 140,000 buffers (>= LANE_MIN_BUFFERS: buffers of <= 128 chunks one per lane,
