@@ -145,6 +145,8 @@ class HipShardOps:
     def unpack_fixed(self, back, spill_back, pos, counts, parts, cap, spill):
         n = pos.numel()
         rep = torch.empty(n, dtype=torch.int64, device=pos.device)
+        if n == 0:  # a rank without files: every slot held a sentinel; the ABI refuses NULL pos / rep
+            return rep
         sb = spill_back if spill_back.numel() else back
         self._chk(self.L.sd_cas_exchange_unpack_fixed_dev(
             self.eng.h, back.data_ptr(), sb.data_ptr(), pos.data_ptr(), counts.data_ptr(), parts,

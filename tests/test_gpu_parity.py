@@ -2377,6 +2377,7 @@ def test_fixed_capacity_exchange_kernels(eng, oracle, world):
     all_to_all of equal blocks is a block transpose.  Grouping == the oracle's canonical,
     keys equal to the sentinels included; then an overflowing part sets the flag."""
     from spacedrive_amd.shard import HipShardOps, fixed_capacity, range_start
+    from tests.exchange_ref import emulate_fixed_exchange
     ops = HipShardOps(eng)
     rng = np.random.default_rng(50 + world)
     pool = rng.integers(0, 2 ** 64, 60_000, dtype=np.uint64)
@@ -2386,35 +2387,13 @@ def test_fixed_capacity_exchange_kernels(eng, oracle, world):
     keys = pool[rng.integers(0, len(pool), 200_003)]
     cuts = [len(keys) * r // world for r in range(world + 1)]
     cap, spill = fixed_capacity(max(cuts[r + 1] - cuts[r] for r in range(world)), world)
-    sent = []
-    for r in range(world):
-        k = dev64(keys[cuts[r]:cuts[r + 1]])
-        pk, pp, cnt = ops.partition(k, world)
-        rows, srows, ovf = ops.pack_fixed(pk, pp, cnt, world, cap, spill, cuts[r])
-        sent.append((pp, cnt, rows.view(world, cap, 3), srows.view(world, spill, 3), ovf))
-    assert all(int(s[4].item()) == 0 for s in sent)
-    backs = []
-    objects = 0
-    for d in range(world):  # receiver d: block d of every sender, main then spill
-        rr = torch.cat([s[2][d] for s in sent] + [s[3][d] for s in sent])
-        rk, rv, nsent = ops.split_fixed(rr, range_start(d + 1, world))
-        ku = rr[:, 0].cpu().numpy().view(np.uint32).astype(np.uint64) | (
-            rr[:, 1].cpu().numpy().view(np.uint32).astype(np.uint64) << np.uint64(32))
-        pad = ku == np.uint64(range_start(d + 1, world))
-        assert int(nsent.item()) == int(pad.sum())
-        got = rk.cpu().numpy().view(np.uint64)
-        want = np.where(pad, np.uint64(range_start(d + 1, world)) + np.arange(len(ku), dtype=np.uint64), ku)
-        assert (got == want).all()  # padding spread to distinct keys, real keys untouched
-        out, obj = ops.group_min_dev(rk, rv)
-        objects += int(obj.item()) - int(nsent.item())
-        backs.append(out)
+    # the world loop (every sender's pack, every receiver's split checked against the
+    # sentinel rule + group_min, the mirror unpack): tests/exchange_ref.py
+    flags, objects, rep = emulate_fixed_exchange(ops, keys, world, cap, spill)
+    assert flags == [0] * world
     orep, oobj = oracle.group_canonical(keys)
     assert objects == oobj
-    for r in range(world):  # mirror: sender r gets block r of every receiver's reps
-        back = torch.cat([b[:world * cap].view(world, cap)[r] for b in backs])
-        sback = torch.cat([b[world * cap:].view(world, spill)[r] for b in backs])
-        rep = ops.unpack_fixed(back, sback, sent[r][0], sent[r][1], world, cap, spill)
-        assert (rep.cpu().numpy() == orep[cuts[r]:cuts[r + 1]].astype(np.int64)).all(), r
+    assert (rep == orep.astype(np.int64)).all()
     # a part beyond cap + spill raises the overflow flag
     k = dev64(np.full(5000, keys[0], dtype=np.uint64))
     pk, pp, cnt = ops.partition(k, world)

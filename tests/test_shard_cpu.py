@@ -200,6 +200,46 @@ def test_sharded_group_fixed_capacity_overflow_falls_back(oracle):
     assert (rep == orep.astype(np.int64)).all()
 
 
+@pytest.mark.parametrize("parts,cap,spill,counts", [
+    (4, 5, 3, [0, 5, 8, 9]),         # empty, exactly cap, exactly cap + spill, one past it
+    (3, 4, 0, [4, 3, 0]),            # no spill block
+    (3, 4, 0, [5, 0, 0]),
+    (7, 3, 2, [0, 1, 2, 3, 4, 5, 6]),
+    (1, 2, 2, [3]),
+])
+def test_vectorised_fixed_references_equal_hostops(parts, cap, spill, counts):
+    """tests/exchange_ref.py's slice-wise pack/unpack/split references (what the GPU tests
+    compare the kernels with at millions of slots) equal HostOps' slot-by-slot loops."""
+    from tests.exchange_ref import pack_fixed_ref, split_fixed_ref, unpack_fixed_ref
+    rng = np.random.default_rng(77)
+    ops = HostOps()
+    n = sum(counts)
+    keys = rng.integers(0, 2 ** 64, n, dtype=np.uint64)
+    pos = rng.permutation(n).astype(np.int32)
+    file0 = 2 ** 32 - n
+    tk, tp = torch.from_numpy(keys.view(np.int64)), torch.from_numpy(pos)
+    tc = torch.tensor(counts, dtype=torch.int64)
+    hr, hs, hflag = ops.pack_fixed(tk, tp, tc, parts, cap, spill, file0)
+    rows, srows, flag = pack_fixed_ref(keys, pos, counts, parts, cap, spill, file0)
+    assert (hr.numpy().view(np.uint32) == rows).all()
+    assert (hs.numpy().view(np.uint32).reshape(-1, 3) == srows).all()
+    assert int(hflag.item()) == flag == int(max(counts) > cap + spill)
+    back = rng.integers(0, 2 ** 32, parts * cap, dtype=np.uint64).astype(np.uint32)
+    sback = rng.integers(0, 2 ** 32, parts * spill, dtype=np.uint64).astype(np.uint32)
+    hrep = ops.unpack_fixed(torch.from_numpy(back.view(np.int32)), torch.from_numpy(sback.view(np.int32)),
+                            tp, tc, parts, cap, spill).numpy()
+    rep, defined = unpack_fixed_ref(back, sback, pos, counts, parts, cap, spill)
+    assert defined.sum() == sum(min(c, cap + spill) for c in counts)
+    assert (hrep[defined] == rep[defined]).all()
+    from spacedrive_amd.shard import range_start
+    for q in range(parts):  # receiver q's view of this one sender: its main block, then its spill block
+        rr = np.concatenate([rows.reshape(parts, cap, 3)[q], srows.reshape(parts, spill, 3)[q]])
+        hk, hv, hn = ops.split_fixed(torch.from_numpy(rr.view(np.int32).copy()), range_start(q + 1, parts))
+        k, v, nsent = split_fixed_ref(rr, range_start(q + 1, parts))
+        assert (hk.numpy().view(np.uint64) == k).all() and (hv.numpy().view(np.uint32) == v).all()
+        assert int(hn.item()) == nsent == cap + spill - min(counts[q], cap + spill)
+
+
 def test_range_part_boundaries():
     k = np.array([0, 1, 2 ** 62, 2 ** 63 - 1, 2 ** 63, 3 * 2 ** 62, 2 ** 64 - 1], dtype=np.uint64)
     assert range_part(k, 2).tolist() == [0, 0, 0, 0, 1, 1, 1]

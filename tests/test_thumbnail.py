@@ -89,3 +89,148 @@ def test_device_batches_vs_oracle(eng):
             assert not rec[i, len(path):].any(), i  # NUL padding
     with pytest.raises(sd.CasError):
         eng.thumbnail_paths(keys, "/srv/sd/thumbnails/ephemeral/", 32, out)
+
+
+# ---- the device batch formatters off their happy path: every prefix alignment, the tight
+# stride, the grid-stride loops, the refusals.  Every byte of every record is compared.
+
+TAIL = 3 + 1 + 16 + 5  # shard '/' cas_id ".webp"
+HEX = np.frombuffer(b"0123456789abcdef", dtype=np.uint8)
+
+
+def roundup16(x: int) -> int:
+    return (x + 15) // 16 * 16
+
+
+def hex_table(hk: np.ndarray) -> np.ndarray:
+    """[n, 16] uint8: the 16 lowercase hex chars of each u64 key, by a nibble table"""
+    b = hk.astype(">u8").view(np.uint8).reshape(len(hk), 8)
+    return HEX[np.stack([b >> 4, b & 15], axis=-1).reshape(len(hk), 16)]
+
+
+def records(prefix: bytes, hexes: np.ndarray, stride: int) -> np.ndarray:
+    """[n, stride] uint8: prefix ‖ shard ‖ '/' ‖ cas_id ‖ ".webp", NUL-padded"""
+    n, p = len(hexes), len(prefix)
+    rec = np.zeros((n, stride), dtype=np.uint8)
+    rec[:, :p] = np.frombuffer(prefix, dtype=np.uint8)
+    rec[:, p:p + 3] = hexes[:, :3]
+    rec[:, p + 3] = ord("/")
+    rec[:, p + 4:p + 20] = hexes
+    rec[:, p + 20:p + 25] = np.frombuffer(b".webp", dtype=np.uint8)
+    return rec
+
+
+def raw_paths(eng, keys, prefix: bytes, stride: int, out) -> None:
+    """sd_cas_thumbnail_paths_dev with the prefix as raw bytes (any byte but NUL)"""
+    import torch
+    eng._check(eng.L.sd_cas_thumbnail_paths_dev(eng.h, keys.data_ptr(), keys.numel(), prefix, stride,
+                                                out.data_ptr(), int(torch.cuda.current_stream().cuda_stream)),
+               "thumbnail_paths_dev")
+
+
+@pytest.fixture(scope="module")
+def sweep_keys():
+    rng = np.random.default_rng(60)
+    hk = rng.integers(0, 2 ** 64 - 1, 300, dtype=np.uint64, endpoint=True)
+    hk[:len(KEYS)] = np.array(KEYS, dtype=np.uint64)
+    cas_ids = [f"{int(k):016x}" for k in hk]
+    tails = np.frombuffer("".join(py_shard_hex(c) + "/" + c + ".webp" for c in cas_ids).encode(),
+                          dtype=np.uint8).reshape(len(hk), TAIL)
+    # the vectorised nibble table of the large batches equals the formatted strings here
+    assert (records(b"", hex_table(hk), 32)[:, :TAIL] == tails).all()
+    return hk, cas_ids, tails
+
+
+def test_hex_table_vs_format():
+    hk = np.array(KEYS, dtype=np.uint64)
+    assert hex_table(hk).tobytes() == "".join(f"{k:016x}" for k in KEYS).encode()
+
+
+@pytest.mark.gpu
+def test_device_paths_prefix_sweep(eng, sweep_keys):
+    """Every prefix length 0..70 (each plen % 4 and % 16: the word that holds the prefix's
+    last 1-3 bytes and the tail's first, prefixes ending on a quad) and the lengths around
+    kMaxPrefix = 1024, at the tight stride roundup16(plen + 26), the next multiple of 16 and
+    (six lengths) 2048; prefix bytes 1..255.  Every record, whole, against the oracle's
+    shard and the cas_id; out is prefilled so an unwritten byte shows."""
+    import torch
+    hk, cas_ids, tails = sweep_keys
+    n = len(hk)
+    keys = torch.from_numpy(hk.view(np.int64)).cuda()
+    rng = np.random.default_rng(61)
+    for plen in list(range(71)) + [1007, 1008, 1009, 1022, 1023, 1024]:
+        prefix = rng.integers(1, 256, plen, dtype=np.uint8).tobytes()
+        tight = roundup16(plen + TAIL + 1)
+        for stride in [tight, tight + 16] + ([2048] if plen in (0, 3, 16, 70, 1007, 1024) else []):
+            out = torch.full((n * stride,), 0xAB, dtype=torch.uint8, device="cuda")
+            raw_paths(eng, keys, prefix, stride, out)
+            want = np.zeros((n, stride), dtype=np.uint8)
+            want[:, :plen] = np.frombuffer(prefix, dtype=np.uint8)
+            want[:, plen:plen + TAIL] = tails
+            got = out.cpu().numpy().reshape(n, stride)
+            assert (got == want).all(), (plen, stride, np.argwhere(got != want)[:4].tolist())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lib", [None, LIB])
+def test_device_paths_real_consumer(eng, sweep_keys, lib):
+    """The same through thumbnail_dir and py_thumbnail_path for every data dir of the host
+    tests, at the tight stride: ties the arbitrary-prefix sweep to the real consumer."""
+    import torch
+    hk, cas_ids, _ = sweep_keys
+    n = len(hk)
+    keys = torch.from_numpy(hk.view(np.int64)).cuda()
+    for data_dir in DIRS:
+        prefix = sdcas.thumbnail_dir(data_dir, lib)
+        stride = roundup16(len(prefix.encode()) + TAIL + 1)
+        out = torch.full((n * stride,), 0xAB, dtype=torch.uint8, device="cuda")
+        eng.thumbnail_paths(keys, prefix, stride, out)
+        want = b"".join(py_thumbnail_path(data_dir, c, lib).encode().ljust(stride, b"\0") for c in cas_ids)
+        assert out.cpu().numpy().tobytes() == want, data_dir
+
+
+@pytest.mark.gpu
+def test_device_batches_grid_stride(eng):
+    """Past the launches' 8,192 x 256 lanes: 70,001 records of 512 B (2.24 M quads) and
+    2,100,001 cas_ids, every byte against the nibble table."""
+    import torch
+    rng = np.random.default_rng(62)
+    n = 2_100_001
+    hk = rng.integers(0, 2 ** 64 - 1, n, dtype=np.uint64, endpoint=True)
+    hk[:len(KEYS)] = np.array(KEYS, dtype=np.uint64)
+    keys = torch.from_numpy(hk.view(np.int64)).cuda()
+    hexes = torch.full((16 * n,), 0xAB, dtype=torch.uint8, device="cuda")
+    eng.keys_to_hex(keys, hexes)
+    table = hex_table(hk)
+    assert n > 8192 * 256 and (hexes.cpu().numpy().reshape(n, 16) == table).all()
+    m, stride = 70_001, 512
+    prefix = sdcas.thumbnail_dir("/home/u/.local/share/spacedrive", LIB)
+    assert m * (stride // 16) > 8192 * 256
+    out = torch.full((m * stride,), 0xAB, dtype=torch.uint8, device="cuda")
+    eng.thumbnail_paths(keys[:m], prefix, stride, out)
+    assert (out.cpu().numpy().reshape(m, stride) == records(prefix.encode(), table[:m], stride)).all()
+
+
+@pytest.mark.gpu
+def test_device_batches_refusals(eng):
+    """A stride below the tight minimum, above 2048 or off a multiple of 16, a prefix past
+    1024 bytes and a misaligned output are refused and nothing is written; n = 0 is fine."""
+    import torch
+    n = 16
+    keys = torch.arange(n, dtype=torch.int64, device="cuda")
+    out = torch.full((n * 2064 + 16,), 0xAB, dtype=torch.uint8, device="cuda")
+    prefix = b"p" * 30
+    tight = roundup16(len(prefix) + TAIL + 1)
+    assert tight == 64
+    for pre, stride, o in [(prefix, tight - 16, out), (prefix, 2064, out), (b"short", 40, out),
+                           (b"q" * 1025, 2048, out), (prefix, tight, out[8:])]:
+        with pytest.raises(sd.CasError):
+            raw_paths(eng, keys, pre, stride, o)
+        assert bool((out == 0xAB).all()), (len(pre), stride)
+    with pytest.raises(sd.CasError):
+        eng.keys_to_hex(keys, out[8:])
+    assert bool((out == 0xAB).all())
+    empty = torch.empty(0, dtype=torch.int64, device="cuda")
+    raw_paths(eng, empty, prefix, tight, out)
+    eng.keys_to_hex(empty, out)
+    assert bool((out == 0xAB).all())
