@@ -334,10 +334,15 @@ int sd_cas_group_chunked_dev(sd_cas_ctx* ctx, const uint32_t* d_rep, size_t n, u
  *               existing Object (mod.rs:202-238; find() = the lowest Object id), and
  *               SD_CAS_NO_OBJECT when dropped or not reached;
  *   d_action[i] SD_CAS_LINK_*.
- * h_step_counts (host, 2 x max_steps u64): per step (total_created, total_linked) as
- * identifier_job_step returns them (mod.rs:349); an empty row queried again counts one
- * creation in every step that processed it.  *out_steps = steps executed.  Ties inside a
- * step follow HashMap order := ascending row.  Blocking; n < 2^32. */
+ * h_step_counts (host, 2 x max_steps u64, max_steps >= sd_cas_identifier_max_steps(n, chunk)
+ * = ceil(n / chunk)): per step (total_created, total_linked) as identifier_job_step returns
+ * them (mod.rs:349); an empty row queried again counts one creation in every step that
+ * processed it.  *out_steps = steps executed.  Exactly the first 2 x ceil(n / chunk) words are
+ * written: the pairs of the executed steps, then zeros for the steps a job that ended early
+ * did not run; with a larger max_steps the words after them are left as they were.  A call
+ * refused for its arguments writes none of them; one refused later (an Object id >= 2^31 found
+ * on the device) leaves them zero.  Ties inside a step follow HashMap order := ascending row
+ * (SURVEY §8c).  Blocking; n < 2^32. */
 #define SD_CAS_ROW_HASHED 0
 #define SD_CAS_ROW_NO_CAS 1
 #define SD_CAS_ROW_ERROR 2

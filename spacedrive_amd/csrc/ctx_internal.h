@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/sd_hip_cas.h"
+#include "sd_debug.h"
 #include "sd_ws.h"
 
 struct DevBuf {
@@ -302,18 +303,43 @@ inline void sd_hex32(const uint8_t d[32], char out[65]) {
   out[64] = 0;
 }
 
+// Device allocations of a context.  The debug library (SD_DBG) ends each one in a
+// patterned 4,096-B tail right after the 256-B round-up of the bytes asked for and keeps it in a
+// process-wide list (sd_hip_cas.cpp): sd_cas_debug_violations() reads every tail back, and a tail
+// is read once more before its buffer is freed, so a kernel that ran past the end of a layout is
+// counted even when the buffer is gone by then.  `name` is what such a report calls the buffer.
+#if SD_DBG
+#define SD_DBG_TAIL_BYTES 4096
+hipError_t sd_dbg_tail_malloc(void** p, size_t bytes, const char* name);
+hipError_t sd_dbg_tail_free(void* p);  // synchronises the buffer's device, reads its tail, frees
+uint64_t sd_dbg_tail_check_all(void);
+inline hipError_t sd_dev_malloc(void** p, size_t bytes, const char* name) {
+  return sd_dbg_tail_malloc(p, bytes, name);
+}
+inline hipError_t sd_dev_free(void* p) { return sd_dbg_tail_free(p); }
+#else
+inline hipError_t sd_dev_malloc(void** p, size_t bytes, const char*) { return hipMalloc(p, bytes); }
+inline hipError_t sd_dev_free(void* p) { return hipFree(p); }
+#endif
+inline const char* sd_buf_name(const sd_cas_ctx* c, const DevBuf& b) {
+  return &b == &c->ws ? "ws" : &b == &c->staging ? "staging" : &b == &c->small ? "small"
+       : &b == &c->io ? "io" : &b == &c->inplace ? "inplace" : &b == &c->cvbuf ? "cvbuf"
+       : &b == &c->regions[0] ? "regions[0]" : &b == &c->regions[1] ? "regions[1]" : "multi";
+}
+
 // Grow a device buffer (on the CURRENT device).  Growing synchronises the device: call
-// outside hot loops / graph capture.
+// outside hot loops / graph capture.  At least 1 MiB, except in the debug library, where the
+// buffer is exactly what the largest layout so far asked for: that layout ends at the tail.
 inline int sd_ensure(sd_cas_ctx* c, DevBuf& b, size_t bytes) {
   if (bytes <= b.bytes) return SD_CAS_OK;
   if (b.p) {
     HIP_TRY(c, hipDeviceSynchronize());
-    HIP_TRY(c, hipFree(b.p));
+    HIP_TRY(c, sd_dev_free(b.p));
     b.p = nullptr;
     b.bytes = 0;
   }
-  size_t want = std::max(bytes, (size_t)1 << 20);
-  if (hipMalloc(&b.p, want) != hipSuccess) {
+  size_t want = SD_DBG ? bytes : std::max(bytes, (size_t)1 << 20);
+  if (sd_dev_malloc(&b.p, want, sd_buf_name(c, b)) != hipSuccess) {
     (void)hipGetLastError();
     return sd_fail(c, SD_CAS_ENOMEM, "hipMalloc(%zu) failed", want);
   }

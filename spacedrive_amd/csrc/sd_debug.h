@@ -5,6 +5,8 @@
 // (debug library only, not part of the ABI header) sums the counters, and the GPU test
 // suite run against the debug library (tools/gpu_r6_final.sh <tag> suite) fails the test after which
 // any counter moved.  Counting instead of trapping keeps a violation from faulting the GPU.
+// The same build ends every device allocation of a context in a checked tail (ctx_internal.h,
+// sd_dev_malloc): a changed tail is one more violation of that sum.
 #ifndef SD_DEBUG_H
 #define SD_DEBUG_H
 

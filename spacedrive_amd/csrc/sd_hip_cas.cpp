@@ -51,10 +51,107 @@ uint32_t sd_dbg_violations_object_stats();
 }  // namespace sdcas
 // debug library only (libsd_hip_cas_debug.so, not in the ABI header): invariant violations
 // counted by the device checks of sd_debug.h since the library was loaded
+// ... plus the allocation tails found changed (below)
+#include "ctx_internal.h"
 extern "C" uint64_t sd_cas_debug_violations(void) {
   return (uint64_t)sd_dbg_violations_group_hash() + sd_dbg_violations_group() +
          sd_dbg_violations_checksum() + sd_dbg_violations_links() + sd_dbg_violations_inplace() +
-         sd_dbg_violations_object_stats();
+         sd_dbg_violations_object_stats() + sd_dbg_tail_check_all();
+}
+
+// The allocation tails of ctx_internal.h: every device buffer of a context is followed by
+// SD_DBG_TAIL_BYTES of a position-dependent pattern (no constant store reproduces it).  A tail
+// found changed counts once, is reported with the buffer's name, the bytes that were asked for
+// and the first changed offset, and is armed again.
+namespace {
+struct DbgTail { void* p; size_t bytes; std::string name; int device; };
+std::mutex g_tail_mu;
+std::vector<DbgTail> g_tails;
+uint64_t g_tail_violations = 0;
+
+inline uint8_t tail_byte(size_t i) { return (uint8_t)((i * 167u + 13u) ^ (i >> 8) ^ 0xA5u); }
+const uint8_t* tail_pattern() {
+  static uint8_t pat[SD_DBG_TAIL_BYTES];
+  static bool made = false;
+  if (!made) {
+    for (size_t i = 0; i < sizeof pat; i++) pat[i] = tail_byte(i);
+    made = true;
+  }
+  return pat;
+}
+// g_tail_mu held, t.device current and idle
+void tail_check_one(const DbgTail& t, const char* when) {
+  uint8_t got[SD_DBG_TAIL_BYTES];
+  uint8_t* tail = (uint8_t*)t.p + up256(t.bytes);
+  if (hipMemcpy(got, tail, sizeof got, hipMemcpyDeviceToHost) != hipSuccess) {
+    (void)hipGetLastError();
+    ++g_tail_violations;
+    printf("SD_CAS tail of %s (%zu bytes) could not be read (%s)\n", t.name.c_str(), t.bytes, when);
+    fflush(stdout);
+    return;
+  }
+  const uint8_t* pat = tail_pattern();
+  if (memcmp(got, pat, sizeof got) == 0) return;
+  size_t first = 0, changed = 0;
+  for (size_t i = sizeof got; i-- > 0;)
+    if (got[i] != pat[i]) { first = i; ++changed; }
+  ++g_tail_violations;
+  printf("SD_CAS workspace overrun (%s): buffer %s of %zu bytes, %zu tail bytes changed, the first "
+         "at offset %zu past its 256-B round-up\n", when, t.name.c_str(), t.bytes, changed, first);
+  fflush(stdout);
+  (void)hipMemcpy(tail, pat, sizeof got, hipMemcpyHostToDevice);
+}
+}  // namespace
+
+hipError_t sd_dbg_tail_malloc(void** p, size_t bytes, const char* name) {
+  hipError_t e = hipMalloc(p, up256(bytes) + SD_DBG_TAIL_BYTES);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> g(g_tail_mu);
+  e = hipMemcpy((uint8_t*)*p + up256(bytes), tail_pattern(), SD_DBG_TAIL_BYTES, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(*p);
+    *p = nullptr;
+    return e;
+  }
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  g_tails.push_back({*p, bytes, name, dev});
+  return hipSuccess;
+}
+
+hipError_t sd_dbg_tail_free(void* p) {
+  {
+    std::lock_guard<std::mutex> g(g_tail_mu);
+    for (size_t i = 0; i < g_tails.size(); i++) {
+      if (g_tails[i].p != p) continue;
+      int cur = 0;
+      (void)hipGetDevice(&cur);
+      (void)hipSetDevice(g_tails[i].device);
+      (void)hipDeviceSynchronize();
+      tail_check_one(g_tails[i], "at free");
+      (void)hipSetDevice(cur);
+      g_tails.erase(g_tails.begin() + i);
+      break;
+    }
+  }
+  return hipFree(p);
+}
+
+uint64_t sd_dbg_tail_check_all(void) {
+  std::lock_guard<std::mutex> g(g_tail_mu);
+  int cur = 0;
+  (void)hipGetDevice(&cur);
+  int synced = -1;  // the list is in allocation order: mostly one device
+  for (const DbgTail& t : g_tails) {
+    if (t.device != synced) {
+      (void)hipSetDevice(t.device);
+      (void)hipDeviceSynchronize();
+      synced = t.device;
+    }
+    tail_check_one(t, "at check");
+  }
+  (void)hipSetDevice(cur);
+  return g_tail_violations;
 }
 #endif
 
@@ -151,10 +248,10 @@ int sd_cas_ctx_create(int device, sd_cas_ctx** out) {
       hipEventCreateWithFlags(&c->packed_h2d, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->packed_done, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->ws_ev, hipEventDisableTiming) != hipSuccess ||
-      hipMalloc((void**)&c->d_scalar, 64) != hipSuccess ||
-      hipMalloc((void**)&c->gtotals, GROUP_TOTALS_WORDS * 4) != hipSuccess ||
+      sd_dev_malloc((void**)&c->d_scalar, 64, "d_scalar") != hipSuccess ||
+      sd_dev_malloc((void**)&c->gtotals, GROUP_TOTALS_WORDS * 4, "gtotals") != hipSuccess ||
       hipMemset(c->gtotals, 0, GROUP_TOTALS_WORDS * 4) != hipSuccess ||
-      hipMalloc((void**)&c->gcursor, 2 * REGION_SET_WORDS * 4) != hipSuccess ||
+      sd_dev_malloc((void**)&c->gcursor, 2 * REGION_SET_WORDS * 4, "gcursor") != hipSuccess ||
       hipMemset(c->gcursor, 0, 2 * REGION_SET_WORDS * 4) != hipSuccess ||
       hipEventCreateWithFlags(&c->region_done[0], hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->region_done[1], hipEventDisableTiming) != hipSuccess ||
@@ -226,17 +323,17 @@ void sd_cas_ctx_destroy(sd_cas_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
-  if (c->ws.p) (void)hipFree(c->ws.p);
-  if (c->staging.p) (void)hipFree(c->staging.p);
-  if (c->small.p) (void)hipFree(c->small.p);
-  if (c->cvbuf.p) (void)hipFree(c->cvbuf.p);
-  if (c->io.p) (void)hipFree(c->io.p);
-  if (c->inplace.p) (void)hipFree(c->inplace.p);
-  if (c->d_scalar) (void)hipFree(c->d_scalar);
-  if (c->gtotals) (void)hipFree(c->gtotals);
-  if (c->gcursor) (void)hipFree(c->gcursor);
+  if (c->ws.p) (void)sd_dev_free(c->ws.p);
+  if (c->staging.p) (void)sd_dev_free(c->staging.p);
+  if (c->small.p) (void)sd_dev_free(c->small.p);
+  if (c->cvbuf.p) (void)sd_dev_free(c->cvbuf.p);
+  if (c->io.p) (void)sd_dev_free(c->io.p);
+  if (c->inplace.p) (void)sd_dev_free(c->inplace.p);
+  if (c->d_scalar) (void)sd_dev_free(c->d_scalar);
+  if (c->gtotals) (void)sd_dev_free(c->gtotals);
+  if (c->gcursor) (void)sd_dev_free(c->gcursor);
   for (int k = 0; k < 2; k++) {
-    if (c->regions[k].p) (void)hipFree(c->regions[k].p);
+    if (c->regions[k].p) (void)sd_dev_free(c->regions[k].p);
     if (c->region_done[k]) (void)hipEventDestroy(c->region_done[k]);
     if (c->region_hashed[k]) (void)hipEventDestroy(c->region_hashed[k]);
   }

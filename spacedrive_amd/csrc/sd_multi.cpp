@@ -198,7 +198,7 @@ int sd_cas_multi_group(sd_cas_multi* m, const uint64_t* const* d_keys, const siz
       MHIP(m, i, hipMemcpyAsync(nw.sidx, ob.sidx, n[i] * 4, hipMemcpyDeviceToDevice, c->stream));
       MHIP(m, i, hipMemcpyAsync(nw.gidx, ob.gidx, n[i] * 8, hipMemcpyDeviceToDevice, c->stream));
       MHIP(m, i, hipStreamSynchronize(c->stream));
-      MHIP(m, i, hipFree(c->small.p));
+      MHIP(m, i, sd_dev_free(c->small.p));
       c->small = nb;
     }
   }
@@ -343,8 +343,8 @@ int sd_cas_multi_hash_group_sampled_host(sd_cas_multi* m, const void* h_content,
       (void)hipEventDestroy(h2d[2 * i + s]);
       (void)hipEventDestroy(done[2 * i + s]);
     }
-    if (keys[i].p) (void)hipFree(keys[i].p);
-    if (rep[i].p) (void)hipFree(rep[i].p);
+    if (keys[i].p) (void)sd_dev_free(keys[i].p);
+    if (rep[i].p) (void)sd_dev_free(rep[i].p);
   }
   return result;
 }

@@ -140,14 +140,14 @@ static int cv_capacity(sd_cas_ctx* c, DevBuf& cvb, size_t need_cvs, hipStream_t 
   DevBuf nb;
   const size_t want = std::max<size_t>(need_cvs * 2 * 32, 1 << 16);
   HIP_TRY(c, hipStreamSynchronize(s));
-  if (hipMalloc(&nb.p, want) != hipSuccess) {
+  if (sd_dev_malloc(&nb.p, want, "cvbuf") != hipSuccess) {
     (void)hipGetLastError();
     return fail(c, SD_CAS_ENOMEM, "hipMalloc(%zu) failed", want);
   }
   nb.bytes = want;
   if (cvb.p) {
     HIP_TRY(c, hipMemcpy(nb.p, cvb.p, cvb.bytes, hipMemcpyDeviceToDevice));
-    HIP_TRY(c, hipFree(cvb.p));
+    HIP_TRY(c, sd_dev_free(cvb.p));
   }
   cvb = nb;
   return SD_CAS_OK;
