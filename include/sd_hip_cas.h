@@ -243,6 +243,15 @@ int sd_cas_hash_regions_sampled_dev(sd_cas_ctx* ctx, const void* d_content, uint
                                     uint32_t* d_rep, uint32_t* d_overflow, void* stream);
 int sd_cas_group_regions_dev(sd_cas_ctx* ctx, size_t n, uint32_t* d_rep, uint64_t* out_objects,
                              void* stream);
+/* The fused chain verifies duplicate contents by comparison instead of hashing them (on = 1,
+ * the default): a file with the size and the first and last 32 content bytes of an earlier one
+ * is compared with it over all 57,344 bytes and, when equal, takes its key; when not, it is
+ * hashed after all.  Keys, rep and the Object count are the same either way; on = 0 runs the
+ * plain K1G (an A/B knob).  The counters of the context's last hash_regions call, read only
+ * here (blocks): candidates nominated, verified equal, rehashed (0, 0, 0 with the setter off). */
+int sd_cas_set_dup_verify(sd_cas_ctx* ctx, int on);
+int sd_cas_dup_verify_counters(sd_cas_ctx* ctx, uint64_t* out_candidates, uint64_t* out_verified,
+                               uint64_t* out_rehashed);
 /* Generalised grouping (the receive side of the multi-GPU exchange):
  * d_out[i] = min{ vals[j] : key[j] == key[i] } (vals NULL = identity, i.e. sd_cas_group_dev);
  * *out_objects = distinct keys (blocks when non-NULL).  n < 2^32 (above

@@ -406,6 +406,19 @@ class CasEngine:
                                                     _stream(stream)), "group_regions")
         return int(obj.value) if want_objects else None
 
+    def set_dup_verify(self, on: bool = True) -> None:
+        """The fused chain compares a duplicate candidate's 57,344 bytes with the earlier file's
+        instead of hashing them (default on; identical results either way, off = plain K1G)."""
+        self._check(self.L.sd_cas_set_dup_verify(self.h, 1 if on else 0), "set_dup_verify")
+
+    def dup_verify_counters(self) -> tuple[int, int, int]:
+        """(candidates, verified, rehashed) of the last hash_regions_sampled /
+        hash_group_sampled call (blocks; zeros when that call did not verify duplicates)."""
+        c, v, r = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self.L.sd_cas_dup_verify_counters(self.h, ctypes.byref(c), ctypes.byref(v),
+                                                      ctypes.byref(r)), "dup_verify_counters")
+        return int(c.value), int(v.value), int(r.value)
+
     def group_min(self, keys, vals, out, stream: Optional[int] = None,
                   want_objects: bool = True) -> Optional[int]:
         """out[i] = min{ vals[j] : keys[j] == keys[i] } (vals None = identity)."""

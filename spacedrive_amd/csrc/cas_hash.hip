@@ -25,8 +25,11 @@
 
 #include "blake3_lane.hpp"
 #include "blake3_tree.hpp"
+#include "sd_dup_probe.h"
+#include "sd_group.h"
 #include "sd_kernels.h"
 #include "sd_mix.h"
+#include "sd_ws.h"
 
 namespace sdcas {
 
@@ -186,25 +189,17 @@ struct RegionOut {
   unsigned long long* objects;
 };
 
+// A lane's output: its key, rep[f] = f and its (mixed key, file) row in the region of its
+// coarse bucket.  The whole workgroup calls it (barriers) once every lane has its root: the
+// stack columns are dead by then and their LDS holds the per-bucket ranks.
 template <int B>
-__device__ __forceinline__ void sampled_group_kernel_body(const uint8_t* __restrict__ content,
-                                                          uint64_t stride,
-                                                          const uint64_t* __restrict__ sizes,
-                                                          uint64_t n, uint64_t* __restrict__ keys,
-                                                          RegionOut ro) {
-  __shared__ uint32_t stack_lds[SAMPLED_DEPTH][8][B];
-  const uint64_t f = (uint64_t)blockIdx.x * B + threadIdx.x;
-  const bool live = f < n;
-  uint64_t key = 0;
-  if (live) {  // exactly K1's lane program
-    LdsStack<B> stk{stack_lds, threadIdx.x};
-    const uint4* q = reinterpret_cast<const uint4*>(content + f * stride);
-    key = cas_lane_sampled<B>(q, sizes[f], stk);
+__device__ __forceinline__ void region_epilogue(uint32_t (&stack_lds)[SAMPLED_DEPTH][8][B],
+                                                bool live, uint64_t f, uint64_t key,
+                                                uint64_t* __restrict__ keys, const RegionOut& ro) {
+  if (live) {
     keys[f] = key;
     ro.rep[f] = (uint32_t)f;
   }
-  if (blockIdx.x == 0 && threadIdx.x < 2) ro.objects[threadIdx.x] = 0;
-  // epilogue: the stack columns are dead once every lane has its root
   // REGIONS counters, REGIONS run bases, REGIONS spill offsets, the spill total and base
   uint32_t* hist = &stack_lds[0][0][0];
   uint32_t* base = hist + REGIONS;
@@ -250,6 +245,25 @@ __device__ __forceinline__ void sampled_group_kernel_body(const uint8_t* __restr
   }
 }
 
+template <int B>
+__device__ __forceinline__ void sampled_group_kernel_body(const uint8_t* __restrict__ content,
+                                                          uint64_t stride,
+                                                          const uint64_t* __restrict__ sizes,
+                                                          uint64_t n, uint64_t* __restrict__ keys,
+                                                          RegionOut ro) {
+  __shared__ uint32_t stack_lds[SAMPLED_DEPTH][8][B];
+  const uint64_t f = (uint64_t)blockIdx.x * B + threadIdx.x;
+  const bool live = f < n;
+  uint64_t key = 0;
+  if (live) {  // exactly K1's lane program
+    LdsStack<B> stk{stack_lds, threadIdx.x};
+    const uint4* q = reinterpret_cast<const uint4*>(content + f * stride);
+    key = cas_lane_sampled<B>(q, sizes[f], stk);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 2) ro.objects[threadIdx.x] = 0;
+  region_epilogue<B>(stack_lds, live, f, key, keys, ro);
+}
+
 extern "C" __global__ void __launch_bounds__(SAMPLED_BLOCK)
 sd_cas_sampled_group_kernel(const uint8_t* __restrict__ content, uint64_t stride,
                             const uint64_t* __restrict__ sizes, uint64_t n,
@@ -262,6 +276,207 @@ sd_cas_sampled_group_kernel_256(const uint8_t* __restrict__ content, uint64_t st
                                 const uint64_t* __restrict__ sizes, uint64_t n,
                                 uint64_t* __restrict__ keys, RegionOut ro) {
   sampled_group_kernel_body<SAMPLED_BLOCK_NARROW>(content, stride, sizes, n, keys, ro);
+}
+
+// ---- K1V: K1G with duplicate contents verified by comparison, not hashed -----------------
+// Two files of equal size and equal 57,344 content bytes have the same message, so the same
+// key: the second one's 953 compressions buy nothing.  Proving the bytes equal costs one more
+// read of both rows and ~40 VALU instructions per 128-B line against 1,360 to hash it.
+//   1. sd_dup_probe_kernel: a 64-bit probe per file (sd_dup_probe.h: size, first and last 32 B);
+//      the hash grouping gives cand[f] = the smallest file with f's probe.  cand[f] == f: hash
+//      f.  Otherwise f is a candidate duplicate of cand[f] (which is hashed: cand[cand[f]] ==
+//      cand[f]).
+//   2. sd_dup_compact_kernel: list H (to hash) and list C (candidates); the counts stay on the
+//      device.
+//   3. sd_cas_dup_mixed_kernel, K1G's grid + 1 workgroup: hash tiles run K1G's lane program and
+//      epilogue on H[tile * B + lane]; compare tiles take a wave per (f, cand[f]) pair and
+//      write same[f].  Compare tiles lie among the hash tiles, so their loads run beside the
+//      hash waves' VALU work, and at the grid's end, where they fill the last hash round's drain.
+//   4. sd_cas_dup_finish_kernel over C: a verified file takes keys[cand[f]]; an unverified one
+//      (a probe collision) is hashed here, under a wave-level branch; every C file then gets
+//      rep[f] = f and its region row through the same epilogue.
+// The bucket tables after it see the same rows as after K1G, in another order.
+struct DupLists {
+  const uint32_t* cand;  // [n] smallest file with the same probe
+  uint32_t* list_h;      // [n] files to hash (counters[0] of them)
+  uint32_t* list_c;      // [n] candidates (counters[1])
+  uint32_t* same;        // [n] same[f] = 1: f's size and bytes equal cand[f]'s (C files only)
+  uint32_t* counters;    // DUP_COUNTERS words
+  uint32_t tail_tiles;   // compare tiles at the grid's end (the mixed kernel), >= 1
+  // the host's view of this call, in pinned host memory: {seq, candidates, files}, seq stored last
+  volatile uint32_t* note;
+  uint32_t seq, files;
+};
+// counters: files to hash, candidates, verified, rehashed, the mixed kernel's pair queue
+constexpr uint32_t DUP_N_HASH = 0, DUP_N_CAND = 1, DUP_VERIFIED = 2, DUP_REHASHED = 3, DUP_QUEUE = 4;
+
+extern "C" __global__ void __launch_bounds__(256)
+sd_dup_probe_kernel(const uint8_t* __restrict__ content, uint64_t stride,
+                    const uint64_t* __restrict__ sizes, uint64_t n, uint64_t* __restrict__ probes,
+                    uint32_t* __restrict__ counters) {
+  const uint64_t f = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (blockIdx.x == 0 && threadIdx.x < DUP_COUNTERS) counters[threadIdx.x] = 0;
+  if (f < n) probes[f] = dup_probe(sizes[f], content + f * stride);
+}
+
+// One reservation per workgroup and list: a list keeps the file order inside a workgroup's run.
+extern "C" __global__ void __launch_bounds__(256)
+sd_dup_compact_kernel(uint64_t n, DupLists dl) {
+  __shared__ uint32_t wcnt[2][4], base[2];
+  const uint64_t f = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const bool live = f < n;
+  const bool h = live && dl.cand[f] == (uint32_t)f;
+  const bool c = live && !h;
+  const uint64_t bh = __ballot(h), bc = __ballot(c);
+  const uint64_t below = (1ull << lane) - 1ull;
+  if (lane == 0) {
+    wcnt[0][w] = (uint32_t)__popcll(bh);
+    wcnt[1][w] = (uint32_t)__popcll(bc);
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const uint32_t t = wcnt[threadIdx.x][0] + wcnt[threadIdx.x][1] + wcnt[threadIdx.x][2] +
+                       wcnt[threadIdx.x][3];
+    base[threadIdx.x] = t ? atomicAdd(&dl.counters[threadIdx.x ? DUP_N_CAND : DUP_N_HASH], t) : 0u;
+  }
+  __syncthreads();
+  uint32_t oh = base[0] + (uint32_t)__popcll(bh & below);
+  uint32_t oc = base[1] + (uint32_t)__popcll(bc & below);
+  for (uint32_t i = 0; i < w; ++i) {
+    oh += wcnt[0][i];
+    oc += wcnt[1][i];
+  }
+  if (h) dl.list_h[oh] = (uint32_t)f;
+  if (c) dl.list_c[oc] = (uint32_t)f;
+}
+
+// One wave proves or refutes that rows a and b hold the same 57,344 bytes: the lanes read
+// consecutive 16-B quads (1 KiB per load instruction), eight quads of each row per round, and
+// stop at the first round that differs.  The stride padding after a row is never read.
+constexpr uint32_t CMP_QUADS = SAMPLED_CONTENT_LEN / 16;  // 3,584 = 56 per lane
+constexpr uint32_t CMP_UNROLL = 8;
+static_assert(CMP_QUADS % (64 * CMP_UNROLL) == 0, "a row is whole compare rounds");
+__device__ __forceinline__ bool rows_equal(const uint4* __restrict__ a, const uint4* __restrict__ b,
+                                           uint32_t lane) {
+#pragma unroll 1
+  for (uint32_t q = lane; q < CMP_QUADS; q += 64 * CMP_UNROLL) {
+    uint4 x[CMP_UNROLL], y[CMP_UNROLL];
+#pragma unroll
+    for (uint32_t u = 0; u < CMP_UNROLL; ++u) x[u] = a[q + 64 * u];
+#pragma unroll
+    for (uint32_t u = 0; u < CMP_UNROLL; ++u) y[u] = b[q + 64 * u];
+    uint32_t d = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < CMP_UNROLL; ++u)
+      d |= (x[u].x ^ y[u].x) | (x[u].y ^ y[u].y) | (x[u].z ^ y[u].z) | (x[u].w ^ y[u].w);
+    if (__ballot(d != 0)) return false;  // (wave-uniform)
+  }
+  return true;
+}
+
+template <int B>
+__device__ __forceinline__ void dup_mixed_kernel_body(const uint8_t* __restrict__ content,
+                                                      uint64_t stride,
+                                                      const uint64_t* __restrict__ sizes,
+                                                      uint64_t* __restrict__ keys, RegionOut ro,
+                                                      DupLists dl) {
+  __shared__ uint32_t stack_lds[SAMPLED_DEPTH][8][B];
+  const uint32_t n_hash = dl.counters[DUP_N_HASH], n_cand = dl.counters[DUP_N_CAND];
+  // the grid is n / B + 1 workgroups: TH hash tiles, and at least one compare tile
+  const uint32_t G = gridDim.x;
+  const uint32_t TH = (n_hash + B - 1) / B;
+  const uint32_t TC = G - TH;
+  // The last TT workgroups of the grid are compare tiles that run until the pair queue is
+  // empty: they start as the last round of hash tiles drains and fill the slots it frees
+  // (a hash tile is one indivisible ~4 ms; a pair is ~50 us).  The other TC - TT compare tiles
+  // lie evenly among the hash tiles and take one tile's worth of pairs each, so compare loads
+  // run beside the hashing from the start: workgroup b < GI is one where floor(b TI / GI) steps.
+  const uint32_t TT = TC < dl.tail_tiles ? TC : dl.tail_tiles;  // >= 1
+  const uint32_t GI = G - TT, TI = TC - TT;
+  const bool tail = blockIdx.x >= GI;
+  const uint32_t c0 = tail ? 0u : (uint32_t)((uint64_t)blockIdx.x * TI / GI);
+  const uint32_t c1 = tail ? 1u : (uint32_t)(((uint64_t)blockIdx.x + 1) * TI / GI);
+  if (blockIdx.x == 0 && threadIdx.x < 2) ro.objects[threadIdx.x] = 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && dl.note) {
+    dl.note[1] = n_cand;
+    dl.note[2] = dl.files;
+    __threadfence_system();
+    dl.note[0] = dl.seq;
+  }
+  if (c0 == c1) {  // hash tile blockIdx.x - c0: K1G's lane program on list H
+    const uint32_t i = (blockIdx.x - c0) * B + threadIdx.x;
+    const bool live = i < n_hash;
+    uint64_t f = 0, key = 0;
+    if (live) {
+      f = dl.list_h[i];
+      LdsStack<B> stk{stack_lds, threadIdx.x};
+      const uint4* q = reinterpret_cast<const uint4*>(content + f * stride);
+      key = cas_lane_sampled<B>(q, sizes[f], stk);
+    }
+    region_epilogue<B>(stack_lds, live, f, key, keys, ro);
+  } else {  // compare tile: a wave per pair, handed out from one queue over list C
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t k = 0; tail || k < 64u; ++k) {
+      uint32_t p = 0;
+      if (lane == 0) p = atomicAdd(&dl.counters[DUP_QUEUE], 1u);
+      p = __builtin_amdgcn_readfirstlane(p);
+      if (p >= n_cand) break;
+      const uint32_t f = dl.list_c[p], g = dl.cand[f];
+      bool eq = sizes[f] == sizes[g];
+      if (eq)
+        eq = rows_equal(reinterpret_cast<const uint4*>(content + (uint64_t)f * stride),
+                        reinterpret_cast<const uint4*>(content + (uint64_t)g * stride), lane);
+      if (lane == 0) dl.same[f] = eq ? 1u : 0u;
+    }
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(SAMPLED_BLOCK)
+sd_cas_dup_mixed_kernel(const uint8_t* __restrict__ content, uint64_t stride,
+                        const uint64_t* __restrict__ sizes, uint64_t* __restrict__ keys,
+                        RegionOut ro, DupLists dl) {
+  dup_mixed_kernel_body<SAMPLED_BLOCK>(content, stride, sizes, keys, ro, dl);
+}
+
+extern "C" __global__ void __launch_bounds__(SAMPLED_BLOCK_NARROW)
+sd_cas_dup_mixed_kernel_256(const uint8_t* __restrict__ content, uint64_t stride,
+                            const uint64_t* __restrict__ sizes, uint64_t* __restrict__ keys,
+                            RegionOut ro, DupLists dl) {
+  dup_mixed_kernel_body<SAMPLED_BLOCK_NARROW>(content, stride, sizes, keys, ro, dl);
+}
+
+// The grid covers n files; the workgroups past list C's end leave at once.
+extern "C" __global__ void __launch_bounds__(SAMPLED_BLOCK_NARROW)
+sd_cas_dup_finish_kernel(const uint8_t* __restrict__ content, uint64_t stride,
+                         const uint64_t* __restrict__ sizes, uint64_t* __restrict__ keys,
+                         RegionOut ro, DupLists dl) {
+  constexpr int B = SAMPLED_BLOCK_NARROW;
+  __shared__ uint32_t stack_lds[SAMPLED_DEPTH][8][B];
+  const uint32_t n_cand = dl.counters[DUP_N_CAND];
+  if (blockIdx.x * B >= n_cand) return;  // (uniform)
+  const uint32_t i = blockIdx.x * B + threadIdx.x;
+  const bool live = i < n_cand;
+  uint64_t f = 0, key = 0;
+  bool ok = false;
+  if (live) {
+    f = dl.list_c[i];
+    ok = dl.same[f] != 0;
+    if (ok) key = keys[dl.cand[f]];  // written by the mixed kernel's hash tiles
+  }
+  const uint64_t verified = __ballot(ok), failed = __ballot(live && !ok);
+  if ((threadIdx.x & 63u) == 0) {
+    if (verified) atomicAdd(&dl.counters[DUP_VERIFIED], (uint32_t)__popcll(verified));
+    if (failed) atomicAdd(&dl.counters[DUP_REHASHED], (uint32_t)__popcll(failed));
+  }
+  if (failed) {  // (wave-uniform) a probe collision in this wave: those lanes hash their file
+    if (live && !ok) {
+      LdsStack<B> stk{stack_lds, threadIdx.x};
+      const uint4* q = reinterpret_cast<const uint4*>(content + f * stride);
+      key = cas_lane_sampled<B>(q, sizes[f], stk);
+    }
+  }
+  region_epilogue<B>(stack_lds, live, f, key, keys, ro);
 }
 
 // ---- K2: the whole-file (packed) path ------------------------------------------------
@@ -483,6 +698,58 @@ hipError_t hash_sampled_regions(const uint8_t* content, uint64_t stride, const u
     sd_cas_sampled_group_kernel<<<(uint32_t)blocks, SAMPLED_BLOCK, 0, s>>>(content, stride, sizes, n,
                                                                           keys, ro);
   }
+  return hipGetLastError();
+}
+
+DupVerifyWs dup_verify_layout(void* ws, uint64_t n) {
+  WsCarve w(ws);  DupVerifyWs L;
+  L.probes = w.take<uint64_t>(n);  L.cand = w.take<uint32_t>(n);
+  L.list_h = w.take<uint32_t>(n);  L.list_c = w.take<uint32_t>(n);  L.same = w.take<uint32_t>(n);
+  L.counters = w.take<uint32_t>(DUP_COUNTERS);  L.objects = w.take<uint64_t>(1);
+  L.bytes = w.bytes();  return L;
+}
+size_t dup_verify_workspace_bytes(uint64_t n) { return dup_verify_layout(nullptr, n).bytes; }
+
+hipError_t dup_candidates(const uint8_t* content, uint64_t stride, const uint64_t* sizes, uint64_t n,
+                          const DupVerifyWs& L, void* group_ws, uint32_t* totals, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  sd_dup_probe_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, s>>>(content, stride, sizes, n, L.probes,
+                                                                  L.counters);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return hash_group_min(L.probes, nullptr, n, L.cand, L.objects, group_ws, totals, s);
+}
+
+hipError_t hash_sampled_regions_verify(const uint8_t* content, uint64_t stride, const uint64_t* sizes,
+                                       uint64_t n, uint64_t* keys, uint32_t* rep, uint64_t* rkeys,
+                                       uint32_t* rfile, uint32_t* cursor, uint64_t cap,
+                                       uint64_t* spill_keys, uint32_t* spill_file, uint32_t* overflow,
+                                       uint64_t* objects, const DupVerifyWs& L, uint32_t* note,
+                                       uint32_t seq, hipStream_t s, uint32_t cus) {
+  if (n == 0) return hipSuccess;
+  const RegionOut ro{rkeys, rfile, cursor, cap, spill_keys, spill_file, rep, overflow,
+                     (unsigned long long*)objects};
+  const uint64_t blocks = (n + SAMPLED_BLOCK - 1) / SAMPLED_BLOCK;
+  const uint64_t quanta = cus ? (n + (uint64_t)cus * 256 - 1) / ((uint64_t)cus * 256) : 0;
+  const bool narrow = cus && (blocks < cus || (quanta & 1));  // the grid choice of hash_sampled
+  // Tail compare tiles: the last round of hash tiles frees the chip's workgroup slots one by
+  // one over a tile's time, half the slots x that time in all, and a compare tile of B pairs
+  // takes ~0.7 of a hash tile's time beside hash tiles (profiles/dup_verify/): slots / 2 / 0.7
+  const uint32_t slots = (cus ? cus : 256u) * (narrow ? 4u : 2u);
+  const uint32_t tail_tiles = slots * 5u / 7u;  // (>= 1)
+  const DupLists dl{L.cand, L.list_h, L.list_c, L.same, L.counters, tail_tiles, note, seq, (uint32_t)n};
+  sd_dup_compact_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, s>>>(n, dl);
+  if (narrow) {
+    const uint64_t nb = (n + SAMPLED_BLOCK_NARROW - 1) / SAMPLED_BLOCK_NARROW;
+    sd_cas_dup_mixed_kernel_256<<<(uint32_t)nb + 1, SAMPLED_BLOCK_NARROW, 0, s>>>(content, stride, sizes,
+                                                                                 keys, ro, dl);
+  } else {
+    sd_cas_dup_mixed_kernel<<<(uint32_t)blocks + 1, SAMPLED_BLOCK, 0, s>>>(content, stride, sizes, keys,
+                                                                          ro, dl);
+  }
+  const uint64_t fb = (n + SAMPLED_BLOCK_NARROW - 1) / SAMPLED_BLOCK_NARROW;
+  sd_cas_dup_finish_kernel<<<(uint32_t)fb, SAMPLED_BLOCK_NARROW, 0, s>>>(content, stride, sizes, keys,
+                                                                        ro, dl);
   return hipGetLastError();
 }
 

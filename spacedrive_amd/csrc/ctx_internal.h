@@ -149,6 +149,8 @@ class HostPool {
   std::atomic<int> nprivate_{0};
 };
 
+constexpr uint32_t DUPV_SKIP_CALLS = 16, DUPV_MIN_CANDIDATE_SHARE = 32;
+
 struct sd_cas_ctx {
   int device = 0;
   hipStream_t stream = nullptr;  // compute
@@ -164,6 +166,22 @@ struct sd_cas_ctx {
   DevBuf cvbuf;    // file_checksum: one 32-B CV per 64 MiB segment
   DevBuf io;       // device copies of host arrays (sd_cas_identifier_links)
   DevBuf inplace;  // cas_ids from whole contents: classify's lists (ordered across streams like ws)
+  // the fused chain's duplicate verification (sd_cas_set_dup_verify): probes, candidates, lists,
+  // flags and counters of the LAST hash_regions call; a call on another stream waits for that
+  // call's region_hashed event before it refills them
+  DevBuf dupv;
+  bool dup_verify = true;
+  uint64_t dupv_n = 0;            // files of the last verified call (0: none, or the setter was off)
+  hipStream_t dupv_stream = nullptr;
+  // Probing a batch costs ~0.3 ms at 1.31 M files whatever it finds, and pays from ~1 candidate
+  // in 32 files on.  Each verified call leaves {seq, candidates, files} in pinned host memory
+  // (dupv_note, written by its mixed kernel); a later call that finds a new note with fewer
+  // candidates than that runs plain K1G, and so do the next DUPV_SKIP_CALLS - 1 calls, before
+  // one probes again.  Read without a sync: a note not yet written just means "probe".
+  uint32_t* dupv_note = nullptr;
+  uint32_t dupv_seq = 0;   // verified calls enqueued so far
+  uint32_t dupv_seen = 0;  // the last note's seq acted on
+  uint32_t dupv_skip = 0;  // calls left to run without probing
   void* pinned = nullptr;
   size_t pinned_bytes = 0;
   uint64_t* d_scalar = nullptr;  // 8 x u64 scratch for counters
@@ -323,7 +341,7 @@ inline hipError_t sd_dev_free(void* p) { return hipFree(p); }
 #endif
 inline const char* sd_buf_name(const sd_cas_ctx* c, const DevBuf& b) {
   return &b == &c->ws ? "ws" : &b == &c->staging ? "staging" : &b == &c->small ? "small"
-       : &b == &c->io ? "io" : &b == &c->inplace ? "inplace" : &b == &c->cvbuf ? "cvbuf"
+       : &b == &c->io ? "io" : &b == &c->inplace ? "inplace" : &b == &c->cvbuf ? "cvbuf" : &b == &c->dupv ? "dupv"
        : &b == &c->regions[0] ? "regions[0]" : &b == &c->regions[1] ? "regions[1]" : "multi";
 }
 

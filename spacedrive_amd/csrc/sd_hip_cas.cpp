@@ -249,6 +249,7 @@ int sd_cas_ctx_create(int device, sd_cas_ctx** out) {
       hipEventCreateWithFlags(&c->packed_done, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->ws_ev, hipEventDisableTiming) != hipSuccess ||
       sd_dev_malloc((void**)&c->d_scalar, 64, "d_scalar") != hipSuccess ||
+      hipHostMalloc((void**)&c->dupv_note, 64, hipHostMallocDefault) != hipSuccess ||
       sd_dev_malloc((void**)&c->gtotals, GROUP_TOTALS_WORDS * 4, "gtotals") != hipSuccess ||
       hipMemset(c->gtotals, 0, GROUP_TOTALS_WORDS * 4) != hipSuccess ||
       sd_dev_malloc((void**)&c->gcursor, 2 * REGION_SET_WORDS * 4, "gcursor") != hipSuccess ||
@@ -263,6 +264,7 @@ int sd_cas_ctx_create(int device, sd_cas_ctx** out) {
     g_ctx_create_err = "stream/event/scratch creation failed on device " + std::to_string(device);
     return SD_CAS_EHIP;
   }
+  memset(c->dupv_note, 0, 64);
   c->quantum = (size_t)prop.multiProcessorCount * 4 * 64;
   {
     const char* t = getenv("SD_CAS_TRACE");
@@ -329,6 +331,8 @@ void sd_cas_ctx_destroy(sd_cas_ctx* c) {
   if (c->cvbuf.p) (void)sd_dev_free(c->cvbuf.p);
   if (c->io.p) (void)sd_dev_free(c->io.p);
   if (c->inplace.p) (void)sd_dev_free(c->inplace.p);
+  if (c->dupv.p) (void)sd_dev_free(c->dupv.p);
+  if (c->dupv_note) (void)hipHostFree(c->dupv_note);
   if (c->d_scalar) (void)sd_dev_free(c->d_scalar);
   if (c->gtotals) (void)sd_dev_free(c->gtotals);
   if (c->gcursor) (void)sd_dev_free(c->gcursor);
@@ -366,6 +370,16 @@ int sd_cas_set_group_method(sd_cas_ctx* c, int method, uint64_t bucket_target) {
                 (unsigned long long)bucket_target);
   c->group_method = method;
   c->group_target = bucket_target;
+  return SD_CAS_OK;
+}
+
+int sd_cas_set_dup_verify(sd_cas_ctx* c, int on) {
+  if (!c) return SD_CAS_EINVAL;
+  if (on != 0 && on != 1) return fail(c, SD_CAS_EINVAL, "set_dup_verify: %d (0 or 1)", on);
+  c->dup_verify = on != 0;
+  // the next call probes, whatever earlier batches held
+  c->dupv_skip = 0;
+  c->dupv_seen = ((volatile uint32_t*)c->dupv_note)[0];
   return SD_CAS_OK;
 }
 
@@ -578,9 +592,45 @@ int sd_cas_hash_regions_sampled_dev(sd_cas_ctx* c, const void* d_content, uint64
   if (rc) return rc;
   const RegionGroupWs L = region_group_layout(c->regions[k].p, c->region_n[k]);
   uint32_t* cur = c->gcursor + REGION_SET_WORDS * k;
-  hipError_t e = hash_sampled_regions((const uint8_t*)d_content, stride, d_sizes, n, d_keys, d_rep,
+  hipError_t e;
+  bool verify = c->dup_verify;
+  if (verify && c->dupv_skip) {
+    c->dupv_skip--;
+    verify = false;
+  } else if (verify) {  // has an earlier call reported too few candidates to pay for the probe?
+    const volatile uint32_t* note = c->dupv_note;
+    const uint32_t seq = note[0], cand = note[1], files = note[2];
+    if (seq != c->dupv_seen && note[0] == seq) {
+      c->dupv_seen = seq;
+      if ((uint64_t)cand * DUPV_MIN_CANDIDATE_SHARE < files) {
+        c->dupv_skip = DUPV_SKIP_CALLS - 1;
+        verify = false;
+      }
+    }
+  }
+  if (verify) {  // K1V: duplicate contents are compared, not hashed
+    if ((rc = ensure(c, c->dupv, dup_verify_workspace_bytes(n)))) return rc;
+    if ((rc = ensure(c, c->ws, hash_group_workspace_bytes(n)))) return rc;
+    // the last call's lists, on another stream: after its chain (the other set's event)
+    if (c->dupv_n && c->dupv_stream != s && c->region_cur >= 0)
+      HIP_TRY(c, hipStreamWaitEvent(s, c->region_hashed[c->region_cur], 0));
+    const DupVerifyWs D = dup_verify_layout(c->dupv.p, n);
+    HIP_TRY(c, sd_ws_acquire(c, s));  // the probes' grouping runs in ws / gtotals
+    e = dup_candidates((const uint8_t*)d_content, stride, d_sizes, n, D, c->ws.p, c->gtotals, s);
+    HIP_TRY(c, sd_ws_release(c, s));
+    if (e == hipSuccess)
+      e = hash_sampled_regions_verify((const uint8_t*)d_content, stride, d_sizes, n, d_keys, d_rep,
                                       L.rkeys, L.rfile, cur, region_capacity(n), L.spill_keys,
-                                      L.spill_file, d_overflow, L.objects, s, (uint32_t)(c->quantum / 256));
+                                      L.spill_file, d_overflow, L.objects, D, c->dupv_note,
+                                      ++c->dupv_seq, s, (uint32_t)(c->quantum / 256));
+    c->dupv_n = e == hipSuccess ? n : 0;
+    c->dupv_stream = s;
+  } else {
+    e = hash_sampled_regions((const uint8_t*)d_content, stride, d_sizes, n, d_keys, d_rep,
+                             L.rkeys, L.rfile, cur, region_capacity(n), L.spill_keys,
+                             L.spill_file, d_overflow, L.objects, s, (uint32_t)(c->quantum / 256));
+    c->dupv_n = 0;
+  }
   if (e != hipSuccess) {
     (void)hipMemsetAsync(cur, 0, REGION_SET_WORDS * 4, s);  // restore the cursors' invariant
     return fail(c, SD_CAS_EHIP, "hash_regions: %s", hipGetErrorString(e));
@@ -589,6 +639,23 @@ int sd_cas_hash_regions_sampled_dev(sd_cas_ctx* c, const void* d_content, uint64
   c->region_keys[k] = d_keys;
   c->region_cur = k;
   c->region_grouped[k] = false;
+  return SD_CAS_OK;
+}
+
+int sd_cas_dup_verify_counters(sd_cas_ctx* c, uint64_t* out_candidates, uint64_t* out_verified,
+                               uint64_t* out_rehashed) {
+  if (!c || !out_candidates || !out_verified || !out_rehashed) return SD_CAS_EINVAL;
+  uint32_t h[DUP_COUNTERS] = {0};
+  if (c->dupv_n && c->region_cur >= 0) {  // the last hash_regions call verified duplicates
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->region_hashed[c->region_cur], 0));
+    HIP_TRY(c, hipMemcpyAsync(h, dup_verify_layout(c->dupv.p, c->dupv_n).counters, sizeof h,
+                              hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  *out_candidates = h[1];
+  *out_verified = h[2];
+  *out_rehashed = h[3];
   return SD_CAS_OK;
 }
 

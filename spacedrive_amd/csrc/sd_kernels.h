@@ -37,6 +37,28 @@ hipError_t hash_sampled_regions(const uint8_t* content, uint64_t stride, const u
                                 uint32_t* rfile, uint32_t* cursor, uint64_t cap, uint64_t* spill_keys,
                                 uint32_t* spill_file, uint32_t* overflow, uint64_t* objects,
                                 hipStream_t s, uint32_t cus);
+// K1V: the same outputs as hash_sampled_regions with duplicate contents verified by comparison
+// instead of hashed (cas_hash.hip).  A buffer of the context's own (dup_verify_workspace_bytes(n))
+// holds the probes, cand (the smallest file with the same probe), the hash and candidate lists,
+// the verified flags and counters[DUP_COUNTERS]: files to hash, candidates, verified, rehashed.
+// dup_candidates fills probes and cand (the hash grouping: group_ws, totals as hash_group_min);
+// hash_sampled_regions_verify is the rest of the chain and needs neither.  note (pinned host
+// memory, 3 u32, or nullptr): the mixed kernel stores {seq, candidates, n} there, seq last, so
+// the host can see without a sync how many candidates an earlier call found.
+constexpr uint32_t DUP_COUNTERS = 8;
+struct DupVerifyWs {
+  uint64_t* probes; uint32_t *cand, *list_h, *list_c, *same, *counters; uint64_t* objects; size_t bytes;
+};
+DupVerifyWs dup_verify_layout(void* ws, uint64_t n);  // ws == nullptr: measure only (sd_ws.h)
+size_t dup_verify_workspace_bytes(uint64_t n);
+hipError_t dup_candidates(const uint8_t* content, uint64_t stride, const uint64_t* sizes, uint64_t n,
+                          const DupVerifyWs& L, void* group_ws, uint32_t* totals, hipStream_t s);
+hipError_t hash_sampled_regions_verify(const uint8_t* content, uint64_t stride, const uint64_t* sizes,
+                                       uint64_t n, uint64_t* keys, uint32_t* rep, uint64_t* rkeys,
+                                       uint32_t* rfile, uint32_t* cursor, uint64_t cap,
+                                       uint64_t* spill_keys, uint32_t* spill_file, uint32_t* overflow,
+                                       uint64_t* objects, const DupVerifyWs& L, uint32_t* note,
+                                       uint32_t seq, hipStream_t s, uint32_t cus);
 // pinned host -> device copy by a kernel (16-B aligned; else hipMemcpyAsync)
 hipError_t pull_host(void* dst, const void* src, uint64_t bytes, hipStream_t s);
 hipError_t hash_packed(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
