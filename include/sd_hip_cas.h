@@ -252,6 +252,12 @@ int sd_cas_group_regions_dev(sd_cas_ctx* ctx, size_t n, uint32_t* d_rep, uint64_
 int sd_cas_set_dup_verify(sd_cas_ctx* ctx, int on);
 int sd_cas_dup_verify_counters(sd_cas_ctx* ctx, uint64_t* out_candidates, uint64_t* out_verified,
                                uint64_t* out_rehashed);
+/* What the comparison of that call read, beside every candidate's own 57,344 bytes (blocks; zeros
+ * with the setter off): groups = earlier files with at least one candidate, tasks = the runs of
+ * consecutive candidates handed to a wave, references = the reads of an earlier file's bytes
+ * (once per group and once more wherever a task's edge cuts a group). */
+int sd_cas_dup_verify_rows(sd_cas_ctx* ctx, uint64_t* out_groups, uint64_t* out_tasks,
+                           uint64_t* out_references);
 /* Generalised grouping (the receive side of the multi-GPU exchange):
  * d_out[i] = min{ vals[j] : key[j] == key[i] } (vals NULL = identity, i.e. sd_cas_group_dev);
  * *out_objects = distinct keys (blocks when non-NULL).  n < 2^32 (above

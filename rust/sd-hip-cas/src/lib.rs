@@ -107,6 +107,8 @@ extern "C" {
     pub fn sd_cas_set_dup_verify(ctx: *mut sd_cas_ctx, on: c_int) -> c_int;
     pub fn sd_cas_dup_verify_counters(ctx: *mut sd_cas_ctx, out_candidates: *mut u64,
                                       out_verified: *mut u64, out_rehashed: *mut u64) -> c_int;
+    pub fn sd_cas_dup_verify_rows(ctx: *mut sd_cas_ctx, out_groups: *mut u64, out_tasks: *mut u64,
+                                  out_references: *mut u64) -> c_int;
     pub fn sd_cas_group_min_dev(ctx: *mut sd_cas_ctx, d_keys: *const u64, d_vals: *const u32, n: usize,
                                 d_out: *mut u32, out_objects: *mut u64, stream: *mut c_void) -> c_int;
     pub fn sd_cas_partition_dev(ctx: *mut sd_cas_ctx, d_keys: *const u64, n: usize, parts: u32,

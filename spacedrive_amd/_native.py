@@ -53,6 +53,7 @@ SIGNATURES = [
     ("sd_cas_group_regions_dev", _i, [_vp, _sz, _vp, _vp, _vp]),
     ("sd_cas_set_dup_verify", _i, [_vp, _i]),
     ("sd_cas_dup_verify_counters", _i, [_vp, _vp, _vp, _vp]),
+    ("sd_cas_dup_verify_rows", _i, [_vp, _vp, _vp, _vp]),
     ("sd_cas_group_min_dev", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("sd_cas_partition_dev", _i, [_vp, _vp, _sz, _u32, _vp, _vp, _vp, _vp]),
     ("sd_cas_exchange_pack_dev", _i, [_vp, _vp, _vp, _sz, _u64, _vp, _vp]),

@@ -419,6 +419,14 @@ class CasEngine:
                                                       ctypes.byref(r)), "dup_verify_counters")
         return int(c.value), int(v.value), int(r.value)
 
+    def dup_verify_rows(self) -> tuple[int, int, int]:
+        """(groups, tasks, references) of the same call: the comparison read every candidate's
+        row once and an earlier file's row `references` times (blocks; zeros as above)."""
+        g, t, r = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self.L.sd_cas_dup_verify_rows(self.h, ctypes.byref(g), ctypes.byref(t),
+                                                  ctypes.byref(r)), "dup_verify_rows")
+        return int(g.value), int(t.value), int(r.value)
+
     def group_min(self, keys, vals, out, stream: Optional[int] = None,
                   want_objects: bool = True) -> Optional[int]:
         """out[i] = min{ vals[j] : keys[j] == keys[i] } (vals None = identity)."""

@@ -642,10 +642,8 @@ int sd_cas_hash_regions_sampled_dev(sd_cas_ctx* c, const void* d_content, uint64
   return SD_CAS_OK;
 }
 
-int sd_cas_dup_verify_counters(sd_cas_ctx* c, uint64_t* out_candidates, uint64_t* out_verified,
-                               uint64_t* out_rehashed) {
-  if (!c || !out_candidates || !out_verified || !out_rehashed) return SD_CAS_EINVAL;
-  uint32_t h[DUP_COUNTERS] = {0};
+// the counters of the context's last hash_regions call (zeros when it did not verify duplicates)
+static int dup_verify_words(sd_cas_ctx* c, uint32_t (&h)[DUP_COUNTERS]) {
   if (c->dupv_n && c->region_cur >= 0) {  // the last hash_regions call verified duplicates
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamWaitEvent(c->stream, c->region_hashed[c->region_cur], 0));
@@ -653,9 +651,30 @@ int sd_cas_dup_verify_counters(sd_cas_ctx* c, uint64_t* out_candidates, uint64_t
                               hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
+  return SD_CAS_OK;
+}
+
+int sd_cas_dup_verify_counters(sd_cas_ctx* c, uint64_t* out_candidates, uint64_t* out_verified,
+                               uint64_t* out_rehashed) {
+  if (!c || !out_candidates || !out_verified || !out_rehashed) return SD_CAS_EINVAL;
+  uint32_t h[DUP_COUNTERS] = {0};
+  const int rc = dup_verify_words(c, h);
+  if (rc) return rc;
   *out_candidates = h[1];
   *out_verified = h[2];
   *out_rehashed = h[3];
+  return SD_CAS_OK;
+}
+
+int sd_cas_dup_verify_rows(sd_cas_ctx* c, uint64_t* out_groups, uint64_t* out_tasks,
+                           uint64_t* out_references) {
+  if (!c || !out_groups || !out_tasks || !out_references) return SD_CAS_EINVAL;
+  uint32_t h[DUP_COUNTERS] = {0};
+  const int rc = dup_verify_words(c, h);
+  if (rc) return rc;
+  *out_groups = h[5];
+  *out_tasks = h[6];
+  *out_references = h[7];
   return SD_CAS_OK;
 }
 

@@ -40,14 +40,17 @@ hipError_t hash_sampled_regions(const uint8_t* content, uint64_t stride, const u
 // K1V: the same outputs as hash_sampled_regions with duplicate contents verified by comparison
 // instead of hashed (cas_hash.hip).  A buffer of the context's own (dup_verify_workspace_bytes(n))
 // holds the probes, cand (the smallest file with the same probe), the hash and candidate lists,
-// the verified flags and counters[DUP_COUNTERS]: files to hash, candidates, verified, rehashed.
+// the verified flags, the arrays that order the candidates by original (cnt, first, rank, the
+// scan's partial sums) and counters[DUP_COUNTERS]: files to hash, candidates, verified, rehashed,
+// the task queue, groups, tasks, reference rows read.
 // dup_candidates fills probes and cand (the hash grouping: group_ws, totals as hash_group_min);
 // hash_sampled_regions_verify is the rest of the chain and needs neither.  note (pinned host
 // memory, 3 u32, or nullptr): the mixed kernel stores {seq, candidates, n} there, seq last, so
 // the host can see without a sync how many candidates an earlier call found.
 constexpr uint32_t DUP_COUNTERS = 8;
 struct DupVerifyWs {
-  uint64_t* probes; uint32_t *cand, *list_h, *list_c, *same, *counters; uint64_t* objects; size_t bytes;
+  uint64_t* probes; uint32_t *cand, *list_h, *list_c, *same, *cnt, *first, *rank, *partial, *counters;
+  uint64_t* objects; size_t bytes;
 };
 DupVerifyWs dup_verify_layout(void* ws, uint64_t n);  // ws == nullptr: measure only (sd_ws.h)
 size_t dup_verify_workspace_bytes(uint64_t n);
