@@ -501,6 +501,61 @@ int sd_cas_duplicate_report(sd_cas_ctx* ctx, const uint64_t* h_keys, const uint6
                             uint64_t out_totals[8], size_t k, uint32_t* h_top_heads,
                             uint64_t* h_top_waste, uint64_t* out_found);
 
+/* ---- Exact duplicate sets: a grouping split by whole-content checksum ----------------------
+ * A cas_id is a sampled hash by design (cas.rs:31-58): beyond 100 KiB it covers the size and
+ * 57,344 bytes, so two files of one size that agree in the header, the four samples and the
+ * footer share it, land in one Object and count as waste above, however much the rest of them
+ * differs.  The library also produces the BLAKE3 of every file's WHOLE content
+ * (integrity_checksum, validation/hash.rs:11-25; the reference stores it,
+ * validator_job.rs:148-169, and groups by nothing); these calls join the two columns.
+ *
+ * d_rep_exact[i] = min{ j : rep[j] == rep[i] && digest[j] == digest[i] }  (d_rep == NULL: the
+ * digests alone); digest i = d_digests[32 i .. 32 i + 32), d_digests 16-B aligned (the layout
+ * sd_cas_checksums_dev and sd_cas_identify_validate_dev write).  *out_objects (may be NULL) =
+ * the number of distinct (rep, digest) pairs, and after the call that is also the context's
+ * "last grouping" Object count (sd_cas_copy_objects_dev).  d_rep is read as a VALUE only,
+ * never used as an index: any u32 is safe.  d_rep_exact must not overlap d_rep
+ * (SD_CAS_EINVAL).  n == 0 launches nothing.  n < 2^32.  Blocking (one small read-back).
+ * AUTO: one u64 key per row, le64(digest[0..8]) ^ rep * 0x9E3779B97F4A7C15 (digest bytes 8..32
+ * take no part: rows of one rep that differ only there collide, which tests construct; BLAKE3
+ * output is uniform, so real rows collide with probability ~n^2 / 2^65), the context's grouping
+ * (sd_cas_set_group_method) over those keys, then every non-head row's full (rep, digest) is
+ * compared with its head's.  No mismatch: the grouping is exact.  Any mismatch, or WORDS: the
+ * word-wise path regroups by one 8-byte digest word at a time, on the device, exact by
+ * construction (eight inner groupings).  Identical results either way. */
+#define SD_CAS_EXACT_AUTO 0
+#define SD_CAS_EXACT_WORDS 1
+int sd_cas_group_exact_dev(sd_cas_ctx* ctx, const uint32_t* d_rep, const uint8_t* d_digests, size_t n,
+                           uint32_t* d_rep_exact, uint64_t* out_objects, void* stream);
+int sd_cas_set_exact_method(sd_cas_ctx* ctx, int method);
+/* Of the context's last sd_cas_group_exact_dev call: the rows whose fast-path head did not match
+ * them (0 under WORDS), and 1 if the word-wise path ran, else 0. */
+int sd_cas_group_exact_counters(sd_cas_ctx* ctx, uint64_t* out_mismatched_rows, uint64_t* out_fallbacks);
+/* A checksum string (Hash::to_hex of hash.rs:24) <-> its 32 bytes.  from_hex takes exactly 64 hex
+ * digits of either case followed by a NUL, anything else is SD_CAS_EINVAL and `out` is left as it
+ * was; to_hex writes 64 lowercase digits and a NUL. */
+int sd_cas_digest_from_hex(const char* hex, uint8_t out[32]);
+void sd_cas_digest_to_hex(const uint8_t digest[32], char out[65]);
+/* sd_cas_duplicate_report with the checksum column: h_hex holds 65 n bytes in the out_hex layout
+ * of sd_cas_file_checksums / sd_cas_identify_validate_paths (64 hex + NUL per row, "" = no
+ * checksum).  h_rep and out_totals are exactly what sd_cas_duplicate_report returns for the same
+ * keys, sizes and state.  A row is ELIGIBLE when it is HASHED and has a checksum; a non-empty
+ * string that is not 64 hex digits fails the call with SD_CAS_EINVAL before any output is
+ * written.  h_rep_exact[i] = min{ j eligible : key[j] == key[i] && digest[j] == digest[i] } for
+ * an eligible row, SD_CAS_NO_OBJECT for any other; h_copies_exact, out_totals_exact and the top
+ * list are sd_cas_object_stats_dev / sd_cas_top_duplicates_dev over that grouping (ineligible
+ * rows: copies 0, counted nowhere), in the caller's row numbering and with the same ordering
+ * rules.  *out_unconfirmed = the HASHED rows without a checksum: the sampled grouping is all
+ * that is known about them.  When every hashed row is eligible, out_totals[UNIQUE_BYTES] and
+ * out_totals_exact[UNIQUE_BYTES] differ by the bytes the sampled grouping wrongly called
+ * duplicate.  Every output pointer may be NULL (the top arrays both or neither, with
+ * out_found), as in sd_cas_duplicate_report.  Blocking; n < 2^32. */
+int sd_cas_duplicate_report_exact(sd_cas_ctx* ctx, const uint64_t* h_keys, const uint64_t* h_sizes,
+                                  const char* h_hex, const uint8_t* h_state, size_t n, uint32_t* h_rep,
+                                  uint32_t* h_rep_exact, uint32_t* h_copies_exact, uint64_t out_totals[8],
+                                  uint64_t out_totals_exact[8], uint64_t* out_unconfirmed, size_t k,
+                                  uint32_t* h_top_heads, uint64_t* h_top_waste, uint64_t* out_found);
+
 /* Stable LSD radix sort of (u64 key, u32 val) on bits [begin_bit, end_bit).
  * d_vals_in == NULL sorts the identity 0..n-1. */
 int sd_cas_sort_pairs_dev(sd_cas_ctx* ctx, const uint64_t* d_keys_in, const uint32_t* d_vals_in,

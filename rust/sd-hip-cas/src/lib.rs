@@ -46,6 +46,8 @@ pub const SD_CAS_STAT_SIZE_MISMATCH_ROWS: usize = 6;
 pub const SD_CAS_STAT_BAD_ROWS: usize = 7;
 pub const SD_CAS_STAT_COUNT: usize = 8;
 pub const SD_CAS_TOP_MAX: usize = 65536;
+pub const SD_CAS_EXACT_AUTO: c_int = 0;
+pub const SD_CAS_EXACT_WORDS: c_int = 1;
 /// status of a row whose fs::metadata length is 0: no cas_id (file_identifier/mod.rs:78-86)
 pub const SD_CAS_STATUS_NO_CAS: i32 = 1;
 
@@ -184,6 +186,19 @@ extern "C" {
                                    h_state: *const u8, n: usize, h_rep: *mut u32, h_copies: *mut u32,
                                    out_totals: *mut u64, k: usize, h_top_heads: *mut u32,
                                    h_top_waste: *mut u64, out_found: *mut u64) -> c_int;
+    pub fn sd_cas_group_exact_dev(ctx: *mut sd_cas_ctx, d_rep: *const u32, d_digests: *const u8, n: usize,
+                                  d_rep_exact: *mut u32, out_objects: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_cas_set_exact_method(ctx: *mut sd_cas_ctx, method: c_int) -> c_int;
+    pub fn sd_cas_group_exact_counters(ctx: *mut sd_cas_ctx, out_mismatched_rows: *mut u64,
+                                       out_fallbacks: *mut u64) -> c_int;
+    pub fn sd_cas_digest_from_hex(hex: *const c_char, out: *mut u8) -> c_int;
+    pub fn sd_cas_digest_to_hex(digest: *const u8, out: *mut c_char);
+    pub fn sd_cas_duplicate_report_exact(ctx: *mut sd_cas_ctx, h_keys: *const u64, h_sizes: *const u64,
+                                         h_hex: *const c_char, h_state: *const u8, n: usize,
+                                         h_rep: *mut u32, h_rep_exact: *mut u32, h_copies_exact: *mut u32,
+                                         out_totals: *mut u64, out_totals_exact: *mut u64,
+                                         out_unconfirmed: *mut u64, k: usize, h_top_heads: *mut u32,
+                                         h_top_waste: *mut u64, out_found: *mut u64) -> c_int;
     pub fn sd_cas_sort_pairs_dev(ctx: *mut sd_cas_ctx, d_keys_in: *const u64, d_vals_in: *const u32,
                                  n: usize, d_keys_out: *mut u64, d_vals_out: *mut u32, begin_bit: c_int,
                                  end_bit: c_int, stream: *mut c_void) -> c_int;
@@ -338,6 +353,18 @@ pub struct Statistics {
     pub copies: Vec<u32>,
     /// the sets wasting the most space: waste descending, ties by head ascending
     pub top: Vec<DuplicateSet>,
+}
+
+/// `Statistics` twice over the same rows: `sampled` as `HipCas::statistics` returns it (sets
+/// of one cas_id), `exact` over the sets whose whole-content checksums (validation/hash.rs:
+/// 11-25) agree as well.  A Hashed row without a checksum is in `sampled` only and counted in
+/// `unconfirmed`; with none of those, `sampled.total_unique_bytes` and
+/// `exact.total_unique_bytes` differ by the bytes the sampled cas_id wrongly called duplicate.
+#[derive(Clone, Debug, Default, PartialEq, Eq)]
+pub struct ExactStatistics {
+    pub sampled: Statistics,
+    pub exact: Statistics,
+    pub unconfirmed: u64,
 }
 
 /// One context per (job thread, device).  Not Sync; Send is fine.
@@ -581,6 +608,68 @@ impl HipCas {
                 .collect(),
             copies,
         })
+    }
+
+    /// `statistics` with the `integrity_checksum` column (64 hex digits per row, `None` = the
+    /// validator has not reached it): sd_cas_duplicate_report_exact.  `sampled.copies` and
+    /// `sampled.top` stay empty — the sets to act on are `exact.top`.
+    pub fn statistics_exact(&mut self, rows: &[(RowState, u64, Option<&str>)], top_k: usize)
+                            -> io::Result<ExactStatistics> {
+        let n = rows.len();
+        let keys: Vec<u64> = rows.iter().map(|(s, _, _)| if let RowState::Hashed(k) = s { k.0 } else { 0 }).collect();
+        let sizes: Vec<u64> = rows.iter().map(|(_, z, _)| *z).collect();
+        let state: Vec<u8> = rows
+            .iter()
+            .map(|(s, _, _)| match s {
+                RowState::Hashed(_) => SD_CAS_ROW_HASHED,
+                RowState::NoCas => SD_CAS_ROW_NO_CAS,
+                RowState::Error => SD_CAS_ROW_ERROR,
+            })
+            .collect();
+        let mut hex = vec![0u8; 65 * n.max(1)];
+        for (i, (_, _, h)) in rows.iter().enumerate() {
+            if let Some(h) = h {
+                if h.len() != 64 {
+                    return Err(io::Error::new(io::ErrorKind::InvalidInput, "checksum is not 64 hex digits"));
+                }
+                hex[65 * i..65 * i + 64].copy_from_slice(h.as_bytes());
+            }
+        }
+        let (mut rep, mut rep_exact, mut copies) = (vec![0u32; n], vec![0u32; n], vec![0u32; n]);
+        let (mut totals, mut totals_exact) = ([0u64; SD_CAS_STAT_COUNT], [0u64; SD_CAS_STAT_COUNT]);
+        let (mut heads, mut waste) = (vec![0u32; top_k.max(1)], vec![0u64; top_k.max(1)]);
+        let (mut found, mut unconfirmed) = (0u64, 0u64);
+        let rc = unsafe {
+            sd_cas_duplicate_report_exact(self.ctx, keys.as_ptr(), sizes.as_ptr(), hex.as_ptr() as *const c_char,
+                                          state.as_ptr(), n, rep.as_mut_ptr(), rep_exact.as_mut_ptr(),
+                                          copies.as_mut_ptr(), totals.as_mut_ptr(), totals_exact.as_mut_ptr(),
+                                          &mut unconfirmed, top_k, heads.as_mut_ptr(), waste.as_mut_ptr(),
+                                          &mut found)
+        };
+        if rc != 0 {
+            return Err(self.err(rc));
+        }
+        let no_cas = state.iter().filter(|&&s| s == SD_CAS_ROW_NO_CAS).count() as u64;
+        let fill = |t: &[u64; SD_CAS_STAT_COUNT], r: &[u32]| Statistics {
+            total_object_count: t[SD_CAS_STAT_OBJECTS] + no_cas,
+            total_unique_bytes: t[SD_CAS_STAT_UNIQUE_BYTES],
+            total_bytes: t[SD_CAS_STAT_TOTAL_BYTES],
+            hashed_rows: t[SD_CAS_STAT_ROWS],
+            no_cas_rows: no_cas,
+            duplicate_sets: t[SD_CAS_STAT_DUPLICATE_SETS],
+            max_copies: t[SD_CAS_STAT_MAX_COPIES],
+            size_mismatch_rows: t[SD_CAS_STAT_SIZE_MISMATCH_ROWS],
+            object_of: r.iter().map(|&x| (x != SD_CAS_NO_OBJECT).then_some(x as usize)).collect(),
+            copies: Vec::new(),
+            top: Vec::new(),
+        };
+        let sampled = fill(&totals, &rep);
+        let mut exact = fill(&totals_exact, &rep_exact);
+        exact.top = (0..found as usize)
+            .map(|j| DuplicateSet { head: heads[j] as usize, copies: copies[heads[j] as usize], waste: waste[j] })
+            .collect();
+        exact.copies = copies;
+        Ok(ExactStatistics { sampled, exact, unconfirmed })
     }
 
     /// `file_checksum(path)` (validation/hash.rs:11).

@@ -79,6 +79,13 @@ SIGNATURES = [
     ("sd_cas_object_stats_dev", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("sd_cas_top_duplicates_dev", _i, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     ("sd_cas_duplicate_report", _i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("sd_cas_group_exact_dev", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("sd_cas_set_exact_method", _i, [_vp, _i]),
+    ("sd_cas_group_exact_counters", _i, [_vp, _vp, _vp]),
+    ("sd_cas_digest_from_hex", _i, [_cp, _vp]),
+    ("sd_cas_digest_to_hex", None, [_vp, _cp]),
+    ("sd_cas_duplicate_report_exact", _i,
+     [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("sd_cas_sort_pairs_dev", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _i, _i, _vp]),
     ("sd_cas_checksum_dev", _i, [_vp, _vp, _u64, _vp, _vp]),
     ("sd_cas_file_checksum", _i, [_vp, _cp, _cp, ctypes.POINTER(_i)]),

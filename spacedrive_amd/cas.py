@@ -45,6 +45,7 @@ STAT_NAMES = ("rows", "objects", "total_bytes", "unique_bytes", "duplicate_sets"
               "size_mismatch_rows", "bad_rows")
 TOP_MAX = 65536
 TOP_TILE = 16384
+EXACT_AUTO, EXACT_WORDS = 0, 1  # SD_CAS_EXACT_*
 
 
 def key_to_cas_id(key: int) -> str:
@@ -54,6 +55,26 @@ def key_to_cas_id(key: int) -> str:
 
 def cas_id_to_key(cas_id: str) -> int:
     return int(cas_id, 16)
+
+
+def digest_from_hex(hex_digest: str) -> bytes:
+    """sd_cas_digest_from_hex: the 32 bytes of a checksum string (file_checksum's result,
+    Hash::to_hex of hash.rs:24) — exactly 64 hex digits of either case, else ValueError."""
+    raw = hex_digest.encode() if isinstance(hex_digest, str) else bytes(hex_digest)
+    out = ctypes.create_string_buffer(32)
+    if b"\0" in raw or _native.lib().sd_cas_digest_from_hex(raw, ctypes.addressof(out)) != 0:
+        raise ValueError(f"not a 64-hex-digit checksum: {hex_digest!r}")
+    return out.raw
+
+
+def digest_to_hex(digest: bytes) -> str:
+    """sd_cas_digest_to_hex: 64 lowercase hex digits of a 32-byte digest."""
+    d = bytes(digest)
+    if len(d) != 32:
+        raise ValueError(f"a digest has 32 bytes, got {len(d)}")
+    src, out = ctypes.create_string_buffer(d, 32), ctypes.create_string_buffer(65)
+    _native.lib().sd_cas_digest_to_hex(ctypes.addressof(src), out)
+    return out.value.decode()
 
 
 def _ptr(t) -> int:
@@ -140,6 +161,22 @@ class DuplicateReport:
     rep: np.ndarray
     copies: np.ndarray
     totals: dict
+    top_heads: np.ndarray
+    top_waste: np.ndarray
+
+
+@dataclass
+class ExactDuplicateReport:
+    """sd_cas_duplicate_report_exact: rep / totals exactly as duplicate_report gives them (sets
+    of one cas_id); rep_exact / copies_exact / totals_exact / the top list over the sets whose
+    whole-content checksums agree as well (NO_OBJECT / 0 on rows that are not hashed or have no
+    checksum); unconfirmed = hashed rows without a checksum."""
+    rep: np.ndarray
+    rep_exact: np.ndarray
+    copies_exact: np.ndarray
+    totals: dict
+    totals_exact: dict
+    unconfirmed: int
     top_heads: np.ndarray
     top_waste: np.ndarray
 
@@ -621,6 +658,86 @@ class CasEngine:
             ctypes.byref(found)), "duplicate_report")
         return DuplicateReport(rep, copies, {q: int(v) for q, v in zip(STAT_NAMES, totals)},
                                heads[:k], waste[:k])
+
+    EXACT_AUTO, EXACT_WORDS = EXACT_AUTO, EXACT_WORDS
+
+    def set_exact_method(self, method: int = EXACT_AUTO) -> None:
+        """group_exact's path: EXACT_AUTO = fast key + verify, the word-wise path only on a
+        mismatch; EXACT_WORDS = always the word-wise path.  Identical results either way."""
+        self._check(self.L.sd_cas_set_exact_method(self.h, int(method)), "set_exact_method")
+
+    def group_exact(self, rep, digests, rep_exact, stream: Optional[int] = None) -> int:
+        """sd_cas_group_exact_dev: rep_exact[i] = the first row with row i's rep AND 32-byte
+        digest (rep None: the digests alone).  rep / rep_exact int32 [n] device tensors (rep is
+        read as a value only), digests uint8 [32 n] (or [n, 32]), 16-B aligned.  Blocking;
+        returns the number of distinct (rep, digest) pairs."""
+        import torch
+        n = int(rep_exact.numel())
+        _check_dev(rep_exact, (torch.int32, torch.uint32), n, "rep_exact")
+        _check_dev(digests, (torch.uint8,), 32 * n, "digests")
+        if rep is not None:
+            _check_dev(rep, (torch.int32, torch.uint32), n, "rep")
+        obj = ctypes.c_uint64(0)
+        self._check(self.L.sd_cas_group_exact_dev(
+            self.h, _ptr(rep) if rep is not None else None, _ptr(digests), n, _ptr(rep_exact),
+            ctypes.byref(obj), _stream(stream)), "group_exact")
+        return int(obj.value)
+
+    def group_exact_counters(self) -> tuple[int, int]:
+        """(mismatched_rows, fallbacks) of the last group_exact call: the rows whose fast-path
+        head did not match them, and 1 if the word-wise path ran."""
+        m, f = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self.L.sd_cas_group_exact_counters(self.h, ctypes.byref(m), ctypes.byref(f)),
+                    "group_exact_counters")
+        return int(m.value), int(f.value)
+
+    def duplicate_report_exact(self, keys, sizes, digests, state=None, k: int = 0) -> ExactDuplicateReport:
+        """sd_cas_duplicate_report_exact (host arrays): duplicate_report plus the same over the
+        exact sets.  digests: per row the 64-hex checksum string identify_validate /
+        file_checksums return, None (or "") = no checksum."""
+        n = len(keys)
+        kk = np.ascontiguousarray(keys, dtype=np.uint64)
+        sz = _sizes_u64(sizes)
+        if sz.shape != (n,):
+            raise ValueError(f"sizes has shape {sz.shape}, expected ({n},)")
+        if len(digests) != n:
+            raise ValueError(f"{len(digests)} digests for {n} rows")
+        st = None if state is None else np.ascontiguousarray(state, dtype=np.uint8)
+        if st is not None and st.shape != (n,):
+            raise ValueError(f"state has shape {st.shape}, expected ({n},)")
+        hexes = np.zeros(max(n, 1), dtype="S65")
+        for i, d in enumerate(digests):
+            if d:
+                b = d.encode() if isinstance(d, str) else bytes(d)
+                if len(b) > 64 or b"\0" in b:  # (a shorter or non-hex one is the library's EINVAL)
+                    raise ValueError(f"digests[{i}]: not a 64-hex-digit checksum")
+                hexes[i] = b
+        k = int(k)
+        rep = np.zeros(n, dtype=np.uint32)
+        rep_exact = np.zeros(n, dtype=np.uint32)
+        copies = np.zeros(n, dtype=np.uint32)
+        totals = np.zeros(len(STAT_NAMES), dtype=np.uint64)
+        totals_exact = np.zeros(len(STAT_NAMES), dtype=np.uint64)
+        heads = np.zeros(max(k, 1), dtype=np.uint32)
+        waste = np.zeros(max(k, 1), dtype=np.uint64)
+        found, unconfirmed = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self.L.sd_cas_duplicate_report_exact(
+            self.h, _np_ptr(kk), _np_ptr(sz), _np_ptr(hexes), _np_ptr(st) if st is not None else None, n,
+            _np_ptr(rep), _np_ptr(rep_exact), _np_ptr(copies), _np_ptr(totals), _np_ptr(totals_exact),
+            ctypes.byref(unconfirmed), k, _np_ptr(heads), _np_ptr(waste), ctypes.byref(found)),
+            "duplicate_report_exact")
+        return ExactDuplicateReport(rep, rep_exact, copies,
+                                    {q: int(v) for q, v in zip(STAT_NAMES, totals)},
+                                    {q: int(v) for q, v in zip(STAT_NAMES, totals_exact)},
+                                    int(unconfirmed.value), heads[:k], waste[:k])
+
+    def exact_duplicates(self, paths: Sequence[str], k: int = 0) -> ExactDuplicateReport:
+        """identify_validate over the paths (one read per file for cas_id and checksum), then
+        duplicate_report_exact: a row is HASHED when its cas_id was computed, NO_CAS when the
+        file is empty, ERROR otherwise; a hashed row whose checksum failed is unconfirmed."""
+        keys, cas_status, sizes, digests, _ = self.identify_validate(paths)
+        state = np.where(cas_status == 0, 0, np.where(cas_status == STATUS_NO_CAS, 1, 2)).astype(np.uint8)
+        return self.duplicate_report_exact(keys, sizes, digests, state, k)
 
     def keys_to_hex(self, keys, out, stream: Optional[int] = None) -> None:
         """The cas_id column of a device batch: out (uint8, 16 per key, 16-B aligned)."""

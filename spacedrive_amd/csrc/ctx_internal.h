@@ -170,6 +170,11 @@ struct sd_cas_ctx {
   // flags and counters of the LAST hash_regions call; a call on another stream waits for that
   // call's region_hashed event before it refills them
   DevBuf dupv;
+  // the exact duplicate grouping (sd_cas_group_exact_dev): fast keys, word ids and the mismatch
+  // counter, beside ws (which the inner grouping calls use); ordered across streams like ws
+  DevBuf exact;
+  int exact_method = 0;  // SD_CAS_EXACT_* (sd_cas_set_exact_method)
+  uint64_t exact_mismatched = 0, exact_fallbacks = 0;  // of the last group_exact call
   bool dup_verify = true;
   uint64_t dupv_n = 0;            // files of the last verified call (0: none, or the setter was off)
   hipStream_t dupv_stream = nullptr;
@@ -342,6 +347,7 @@ inline hipError_t sd_dev_free(void* p) { return hipFree(p); }
 inline const char* sd_buf_name(const sd_cas_ctx* c, const DevBuf& b) {
   return &b == &c->ws ? "ws" : &b == &c->staging ? "staging" : &b == &c->small ? "small"
        : &b == &c->io ? "io" : &b == &c->inplace ? "inplace" : &b == &c->cvbuf ? "cvbuf" : &b == &c->dupv ? "dupv"
+       : &b == &c->exact ? "exact"
        : &b == &c->regions[0] ? "regions[0]" : &b == &c->regions[1] ? "regions[1]" : "multi";
 }
 
@@ -409,6 +415,11 @@ struct DupReportWs {
   uint64_t *keys, *sizes; uint32_t *rep, *copies; uint8_t* state; uint64_t* hkeys;
   uint32_t *hrows, *minrow; uint64_t* orphans; uint32_t* top_heads; uint64_t *top_waste, *counters; size_t bytes;
 };
+struct ExactWs { uint64_t* keys; uint32_t *ids, *counter; size_t bytes; };
+struct ExactReportWs {
+  uint64_t* ckeys; uint8_t* cdigests; uint32_t *crows, *prior, *crep; uint64_t* sizes; uint8_t* state;
+  uint32_t *rep, *copies, *top_heads; uint64_t* top_waste; size_t bytes;
+};
 struct StagedLayout { size_t packed, sizes, poffs, plens, keys, h2d_bytes, bytes; };
 struct MultiBufs {
   uint64_t* skeys; uint32_t* sidx; uint64_t* gidx; uint64_t* splits; uint64_t* back;
@@ -423,6 +434,8 @@ LinkIoWs sd_link_io_layout(void* base, size_t n, size_t n_seed, bool pre);
 StatsWs sd_stats_layout(void* ws);
 TopWs sd_top_layout(void* ws, uint64_t n, uint64_t m);
 DupReportWs sd_dup_report_layout(void* base, size_t n, bool state, size_t k);
+ExactWs sd_exact_layout(void* base, size_t n);
+ExactReportWs sd_exact_report_layout(void* base, size_t n, size_t m, size_t k);
 }
 
 inline int sd_ensure_pinned(sd_cas_ctx* c, size_t bytes) {

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "sd_checksum.h"
+#include "sd_exact_dups.h"
 #include "sd_group.h"
 #include "sd_kernels.h"
 #include "sd_links.h"
@@ -48,6 +49,7 @@ uint32_t sd_dbg_violations_checksum();
 uint32_t sd_dbg_violations_links();
 uint32_t sd_dbg_violations_inplace();
 uint32_t sd_dbg_violations_object_stats();
+uint32_t sd_dbg_violations_exact_dups();
 }  // namespace sdcas
 // debug library only (libsd_hip_cas_debug.so, not in the ABI header): invariant violations
 // counted by the device checks of sd_debug.h since the library was loaded
@@ -56,7 +58,7 @@ uint32_t sd_dbg_violations_object_stats();
 extern "C" uint64_t sd_cas_debug_violations(void) {
   return (uint64_t)sd_dbg_violations_group_hash() + sd_dbg_violations_group() +
          sd_dbg_violations_checksum() + sd_dbg_violations_links() + sd_dbg_violations_inplace() +
-         sd_dbg_violations_object_stats() + sd_dbg_tail_check_all();
+         sd_dbg_violations_object_stats() + sd_dbg_violations_exact_dups() + sd_dbg_tail_check_all();
 }
 
 // The allocation tails of ctx_internal.h: every device buffer of a context is followed by
@@ -332,6 +334,7 @@ void sd_cas_ctx_destroy(sd_cas_ctx* c) {
   if (c->io.p) (void)sd_dev_free(c->io.p);
   if (c->inplace.p) (void)sd_dev_free(c->inplace.p);
   if (c->dupv.p) (void)sd_dev_free(c->dupv.p);
+  if (c->exact.p) (void)sd_dev_free(c->exact.p);
   if (c->dupv_note) (void)hipHostFree(c->dupv_note);
   if (c->d_scalar) (void)sd_dev_free(c->d_scalar);
   if (c->gtotals) (void)sd_dev_free(c->gtotals);
@@ -1257,6 +1260,220 @@ int sd_cas_duplicate_report(sd_cas_ctx* c, const uint64_t* h_keys, const uint64_
   }
   if (h_rep) HIP_TRY(c, hipMemcpyAsync(h_rep, L.rep, n * 4, hipMemcpyDeviceToHost, s));
   if (h_copies) HIP_TRY(c, hipMemcpyAsync(h_copies, L.copies, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  return SD_CAS_OK;
+}
+
+// ---- exact duplicate sets ----------------------------------------------------------------
+// A cas_id samples a file longer than 100 KiB (cas.rs:31-58); the whole-content BLAKE3 of
+// validation/hash.rs:11-25 does not.  exact_dups.hip joins the two columns.
+
+// c->exact: the fast (or word / pair) keys | the word ids | the mismatch counter
+ExactWs sd_exact_layout(void* base, size_t n) {
+  WsCarve w(base);  ExactWs L;
+  L.keys = w.take<uint64_t>(n);  L.ids = w.take<uint32_t>(n);  L.counter = w.take<uint32_t>(1);
+  L.bytes = w.bytes();  return L;
+}
+// the exact report's device copies (c->io): the m eligible rows compacted (keys | digests | their
+// rows | cas grouping | exact grouping), then per caller row sizes | state | rep | copies, then
+// the top list
+ExactReportWs sd_exact_report_layout(void* base, size_t n, size_t m, size_t k) {
+  WsCarve w(base);  ExactReportWs L;
+  L.ckeys = w.take<uint64_t>(m);  L.cdigests = w.take<uint8_t>(32 * (uint64_t)m);
+  L.crows = w.take<uint32_t>(m);  L.prior = w.take<uint32_t>(m);  L.crep = w.take<uint32_t>(m);
+  L.sizes = w.take<uint64_t>(n);  L.state = w.take<uint8_t>(n);  L.rep = w.take<uint32_t>(n);
+  L.copies = w.take<uint32_t>(n);  L.top_heads = w.take<uint32_t>(k);  L.top_waste = w.take<uint64_t>(k);
+  L.bytes = w.bytes();  return L;
+}
+
+static int hex_nibble(char ch) {
+  return ch >= '0' && ch <= '9' ? ch - '0' : ch >= 'a' && ch <= 'f' ? ch - 'a' + 10
+       : ch >= 'A' && ch <= 'F' ? ch - 'A' + 10 : -1;
+}
+
+int sd_cas_digest_from_hex(const char* hex, uint8_t out[32]) {
+  if (!hex || !out) return SD_CAS_EINVAL;
+  uint8_t d[32];
+  for (int i = 0; i < 32; i++) {  // stops at the first byte that is no hex digit (a NUL included)
+    const int hi = hex_nibble(hex[2 * i]);
+    if (hi < 0) return SD_CAS_EINVAL;
+    const int lo = hex_nibble(hex[2 * i + 1]);
+    if (lo < 0) return SD_CAS_EINVAL;
+    d[i] = (uint8_t)(hi << 4 | lo);
+  }
+  if (hex[64] != 0) return SD_CAS_EINVAL;
+  memcpy(out, d, 32);
+  return SD_CAS_OK;
+}
+
+void sd_cas_digest_to_hex(const uint8_t digest[32], char out[65]) { sd_hex32(digest, out); }
+
+int sd_cas_set_exact_method(sd_cas_ctx* c, int method) {
+  if (!c) return SD_CAS_EINVAL;
+  if (method != SD_CAS_EXACT_AUTO && method != SD_CAS_EXACT_WORDS)
+    return fail(c, SD_CAS_EINVAL, "set_exact_method: method %d", method);
+  c->exact_method = method;
+  return SD_CAS_OK;
+}
+
+int sd_cas_group_exact_counters(sd_cas_ctx* c, uint64_t* out_mismatched_rows, uint64_t* out_fallbacks) {
+  if (!c || !out_mismatched_rows || !out_fallbacks) return SD_CAS_EINVAL;
+  *out_mismatched_rows = c->exact_mismatched;
+  *out_fallbacks = c->exact_fallbacks;
+  return SD_CAS_OK;
+}
+
+// The word-wise path: class = rep (a constant without one), then for each of the four digest
+// words id = group(word) and class = group(class << 32 | id).  By induction the class after word
+// w is the first row with the same rep and words 0..w, so the last one is rep_exact; the last
+// inner grouping's Object count (d_scalar) is the number of distinct (rep, digest) pairs.
+static int group_exact_words(sd_cas_ctx* c, const uint32_t* d_rep, const uint8_t* d_digests, size_t n,
+                             uint32_t* d_rep_exact, const ExactWs& L, hipStream_t s) {
+  int rc;
+  for (uint32_t w = 0; w < 4; w++) {
+    HIP_TRY(c, exact_word_keys(d_digests, w, n, L.keys, s));
+    if ((rc = sd_cas_group_dev(c, L.keys, n, L.ids, nullptr, s))) return rc;
+    HIP_TRY(c, exact_pair_keys(w == 0 ? d_rep : d_rep_exact, L.ids, n, L.keys, s));
+    if ((rc = sd_cas_group_dev(c, L.keys, n, d_rep_exact, nullptr, s))) return rc;
+  }
+  return SD_CAS_OK;
+}
+
+int sd_cas_group_exact_dev(sd_cas_ctx* c, const uint32_t* d_rep, const uint8_t* d_digests, size_t n,
+                           uint32_t* d_rep_exact, uint64_t* out_objects, void* stream) {
+  if (!c) return SD_CAS_EINVAL;
+  if (n >= (1ull << 32) || (n && (!d_digests || !d_rep_exact)))
+    return fail(c, SD_CAS_EINVAL, "group_exact: bad arguments");
+  if ((uintptr_t)d_digests & 15) return fail(c, SD_CAS_EINVAL, "group_exact: digests not 16-B aligned");
+  if (n && d_rep && (uintptr_t)d_rep < (uintptr_t)d_rep_exact + 4 * n &&
+      (uintptr_t)d_rep_exact < (uintptr_t)d_rep + 4 * n)
+    return fail(c, SD_CAS_EINVAL, "group_exact: rep_exact aliases rep");
+  if (c->group_method == SD_CAS_GROUP_HASH && !hash_group_supported(n))
+    return fail(c, SD_CAS_EINVAL, "group_exact: %zu rows exceed the hash grouping's range", n);
+  hipStream_t s = pick(c, stream);
+  c->exact_mismatched = c->exact_fallbacks = 0;
+  if (n == 0) {  // no Objects: the context's count is 0 (a memset, no launch)
+    HIP_TRY(c, sd_ws_acquire(c, s));
+    HIP_TRY(c, hipMemsetAsync(c->d_scalar, 0, 8, s));
+    HIP_TRY(c, sd_ws_release(c, s));
+    c->region_obj_set = -1;
+    if (out_objects) *out_objects = 0;
+    return SD_CAS_OK;
+  }
+  int rc = ensure(c, c->exact, sd_exact_layout(nullptr, n).bytes);
+  if (rc) return rc;
+  const ExactWs L = sd_exact_layout(c->exact.p, n);
+  HIP_TRY(c, sd_ws_acquire(c, s));  // c->exact is ordered with ws: the inner groupings use both
+  uint64_t objects = 0;
+  bool words = c->exact_method == SD_CAS_EXACT_WORDS;
+  if (!words) {
+    uint32_t mismatched = 0;
+    HIP_TRY(c, hipMemsetAsync(L.counter, 0, 4, s));
+    HIP_TRY(c, exact_keys(d_rep, d_digests, n, L.keys, s));
+    if ((rc = sd_cas_group_dev(c, L.keys, n, d_rep_exact, nullptr, s))) return rc;
+    HIP_TRY(c, exact_verify(d_rep, d_digests, d_rep_exact, n, L.counter, false, s));
+    HIP_TRY(c, hipMemcpyAsync(&mismatched, L.counter, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&objects, c->d_scalar, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    c->exact_mismatched = mismatched;
+    words = mismatched != 0;
+  }
+  if (words) {
+    c->exact_fallbacks = 1;
+    if ((rc = group_exact_words(c, d_rep, d_digests, n, d_rep_exact, L, s))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(&objects, c->d_scalar, 8, hipMemcpyDeviceToHost, s));
+#if SD_DBG
+    // (the count lands in L.counter and is not read: a differing row reports itself)
+    HIP_TRY(c, hipMemsetAsync(L.counter, 0, 4, s));
+    HIP_TRY(c, exact_verify(d_rep, d_digests, d_rep_exact, n, L.counter, true, s));
+#endif
+    HIP_TRY(c, hipStreamSynchronize(s));
+  }
+  HIP_TRY(c, sd_ws_release(c, s));
+  if (out_objects) *out_objects = objects;
+  return SD_CAS_OK;
+}
+
+int sd_cas_duplicate_report_exact(sd_cas_ctx* c, const uint64_t* h_keys, const uint64_t* h_sizes,
+                                  const char* h_hex, const uint8_t* h_state, size_t n, uint32_t* h_rep,
+                                  uint32_t* h_rep_exact, uint32_t* h_copies_exact, uint64_t out_totals[8],
+                                  uint64_t out_totals_exact[8], uint64_t* out_unconfirmed, size_t k,
+                                  uint32_t* h_top_heads, uint64_t* h_top_waste, uint64_t* out_found) {
+  if (!c) return SD_CAS_EINVAL;
+  const bool want_top = h_top_heads && h_top_waste;
+  if (n >= (1ull << 32) || (n && (!h_keys || !h_sizes || !h_hex)) || (!h_top_heads != !h_top_waste) ||
+      (want_top && !out_found))
+    return fail(c, SD_CAS_EINVAL, "duplicate_report_exact: bad arguments");
+  if (want_top && k > SD_CAS_TOP_MAX)
+    return fail(c, SD_CAS_EINVAL, "duplicate_report_exact: k = %zu exceeds SD_CAS_TOP_MAX", k);
+  // every checksum is parsed before any output is written: the eligible rows (HASHED, with a
+  // checksum) compacted in ascending row order, so the smallest compacted index of a set is its
+  // smallest row
+  std::vector<uint64_t> ckeys;
+  std::vector<uint8_t> cdig, state(n, (uint8_t)SD_CAS_ROW_ERROR);
+  std::vector<uint32_t> crows;
+  uint64_t unconfirmed = 0;
+  for (size_t i = 0; i < n; i++) {
+    const char* hx = h_hex + 65 * i;
+    const bool hashed = !h_state || h_state[i] == SD_CAS_ROW_HASHED;
+    if (hx[0] == 0) {
+      unconfirmed += hashed ? 1 : 0;
+      continue;
+    }
+    uint8_t d[32];
+    if (sd_cas_digest_from_hex(hx, d))
+      return fail(c, SD_CAS_EINVAL, "duplicate_report_exact: row %zu: malformed checksum", i);
+    if (!hashed) continue;
+    state[i] = SD_CAS_ROW_HASHED;
+    ckeys.push_back(h_keys[i]);
+    crows.push_back((uint32_t)i);
+    cdig.insert(cdig.end(), d, d + 32);
+  }
+  const size_t m = crows.size();
+  int rc;
+  if (h_rep || out_totals)
+    if ((rc = sd_cas_duplicate_report(c, h_keys, h_sizes, h_state, n, h_rep, nullptr, out_totals, 0,
+                                      nullptr, nullptr, nullptr)))
+      return rc;
+  if (out_found) *out_found = 0;
+  if (out_unconfirmed) *out_unconfirmed = unconfirmed;
+  if (out_totals_exact)
+    for (int j = 0; j < SD_CAS_STAT_COUNT; j++) out_totals_exact[j] = 0;
+  if (n == 0) {
+    if (want_top)
+      for (size_t j = 0; j < k; j++) { h_top_heads[j] = SD_CAS_NO_OBJECT; h_top_waste[j] = 0; }
+    return SD_CAS_OK;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t kk = want_top ? k : 0;
+  if ((rc = ensure(c, c->io, sd_exact_report_layout(nullptr, n, m, kk).bytes))) return rc;
+  const ExactReportWs L = sd_exact_report_layout(c->io.p, n, m, kk);
+  hipStream_t s = c->stream;
+  HIP_TRY(c, hipMemcpyAsync(L.sizes, h_sizes, n * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(L.state, state.data(), n, hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemsetAsync(L.rep, 0xFF, n * 4, s));
+  if (m) {
+    HIP_TRY(c, hipMemcpyAsync(L.ckeys, ckeys.data(), m * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(L.cdigests, cdig.data(), m * 32, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(L.crows, crows.data(), m * 4, hipMemcpyHostToDevice, s));
+    if ((rc = sd_cas_group_dev(c, L.ckeys, m, L.prior, nullptr, s))) return rc;
+    if ((rc = sd_cas_group_exact_dev(c, L.prior, L.cdigests, m, L.crep, nullptr, s))) return rc;
+    HIP_TRY(c, exact_scatter(L.crep, L.crows, m, L.rep, s));
+  }
+  uint64_t totals[SD_CAS_STAT_COUNT];
+  if ((rc = object_stats_impl(c, L.rep, L.sizes, L.state, n, L.copies, nullptr, totals, s))) return rc;
+  if (out_totals_exact)
+    for (int j = 0; j < SD_CAS_STAT_COUNT; j++) out_totals_exact[j] = totals[j];
+  if (want_top) {
+    if ((rc = sd_cas_top_duplicates_dev(c, L.rep, L.sizes, L.copies, n, k, L.top_heads, L.top_waste, out_found, s)))
+      return rc;
+    if (k) {
+      HIP_TRY(c, hipMemcpyAsync(h_top_heads, L.top_heads, k * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(c, hipMemcpyAsync(h_top_waste, L.top_waste, k * 8, hipMemcpyDeviceToHost, s));
+    }
+  }
+  if (h_rep_exact) HIP_TRY(c, hipMemcpyAsync(h_rep_exact, L.rep, n * 4, hipMemcpyDeviceToHost, s));
+  if (h_copies_exact) HIP_TRY(c, hipMemcpyAsync(h_copies_exact, L.copies, n * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   return SD_CAS_OK;
 }
