@@ -25,6 +25,7 @@
 
 #include "blake3_lane.hpp"
 #include "blake3_tree.hpp"
+#include "sd_debug.h"
 #include "sd_dup_probe.h"
 #include "sd_dup_runs.h"
 #include "sd_group.h"
@@ -298,7 +299,9 @@ sd_cas_sampled_group_kernel_256(const uint8_t* __restrict__ content, uint64_t st
 //      DUP_RUN_K entries of list C (sd_dup_runs.h), read the original once per run of its
 //      copies and write same[f].  Compare tiles lie among the hash tiles, so their loads run
 //      beside the hash waves' VALU work, and at the grid's end, where they fill the last hash
-//      round's drain.
+//      round's drain.  Which workgroup does what is either fixed before launch (dup_tile_of) or,
+//      for large grids, taken at run time by each workgroup as it starts: at most one compare
+//      workgroup of one wave per SIMD on a CU, the others hashing (sd_dup_runs.h).
 //   4. sd_cas_dup_finish_kernel over C: a verified file takes keys[cand[f]]; an unverified one
 //      (a probe collision) is hashed here, under a wave-level branch; every C file then gets
 //      rep[f] = f and its region row through the same epilogue.
@@ -312,23 +315,32 @@ struct DupLists {
   uint32_t* first;       // [n] first[g] = list C slot of g's first candidate (cnt's scan)
   uint32_t* rank;        // [n] rank[f] = f's place among cand[f]'s candidates (C files only)
   uint32_t* counters;    // DUP_COUNTERS words
-  uint32_t tail_tiles;   // compare tiles at the grid's end (the mixed kernel), >= 1
+  uint32_t* cu;          // DUP_CU_SLOTS words: compare workgroups resident per CU (run-time roles)
+  uint32_t tail_tiles;   // compare tiles at the grid's end (the mixed kernel), >= 1; 0: roles are
+                         // taken at run time (sd_dup_runs.h)
+  uint32_t slots;        // workgroups of the main kernel that the chip holds at once
   // the host's view of this call, in pinned host memory: {seq, candidates, files}, seq stored last
   volatile uint32_t* note;
   uint32_t seq, files;
 };
 // counters: files to hash, candidates, verified, rehashed, the mixed kernel's task queue,
-// groups (originals with a candidate), tasks run, reference rows read (one per run of a task)
+// groups (originals with a candidate), tasks run, reference rows read (one per run of a task);
+// run-time roles: the hash-tile queue, compare workgroups started; the debug library's conservation
+// check: hash tiles run, and how many the launched grid shape has
 constexpr uint32_t DUP_N_HASH = 0, DUP_N_CAND = 1, DUP_VERIFIED = 2, DUP_REHASHED = 3, DUP_QUEUE = 4,
-                   DUP_GROUPS = 5, DUP_TASKS = 6, DUP_REFS = 7;
-static_assert(DUP_REFS < DUP_COUNTERS, "counters");
+                   DUP_GROUPS = 5, DUP_TASKS = 6, DUP_REFS = 7, DUP_HASH_QUEUE = 8, DUP_COMPARE_WGS = 9,
+                   DUP_TILES_RUN = 10, DUP_TILES_WANT = 11;
+static_assert(DUP_TILES_RUN < DUP_TILES_WANT && DUP_TILES_WANT < DUP_COUNTERS, "counters");
 
 extern "C" __global__ void __launch_bounds__(256)
 sd_dup_probe_kernel(const uint8_t* __restrict__ content, uint64_t stride,
                     const uint64_t* __restrict__ sizes, uint64_t n, uint64_t* __restrict__ probes,
-                    uint32_t* __restrict__ counters, uint32_t* __restrict__ cnt) {
+                    uint32_t* __restrict__ counters, uint32_t* __restrict__ cu,
+                    uint32_t* __restrict__ cnt) {
   const uint64_t f = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (blockIdx.x == 0 && threadIdx.x < DUP_COUNTERS) counters[threadIdx.x] = 0;
+  if (blockIdx.x == 0)
+    for (uint32_t i = threadIdx.x; i < DUP_CU_SLOTS; i += 256) cu[i] = 0;
   if (f < n) {
     probes[f] = dup_probe(sizes[f], content + f * stride);
     cnt[f] = 0;
@@ -481,6 +493,13 @@ __device__ __forceinline__ uint32_t dup_compare_task(const uint8_t* __restrict__
   return runs;
 }
 
+// The CU this wave runs on, as a slot of DupLists::cu.
+__device__ __forceinline__ uint32_t dup_this_cu_slot() {
+  constexpr int HW_REG_HW_ID = 4, HW_REG_XCC_ID = 20, WHOLE = 31 << 11;  // simm16: id | offset << 6 | (size - 1) << 11
+  return dup_cu_slot(__builtin_amdgcn_s_getreg(HW_REG_XCC_ID | WHOLE),
+                     __builtin_amdgcn_s_getreg(HW_REG_HW_ID | WHOLE));
+}
+
 template <int B>
 __device__ __forceinline__ void dup_mixed_kernel_body(const uint8_t* __restrict__ content,
                                                       uint64_t stride,
@@ -498,7 +517,48 @@ __device__ __forceinline__ void dup_mixed_kernel_body(const uint8_t* __restrict_
   // compare tiles lie evenly among the hash tiles and take one tile's worth of entries each (a
   // lane's worth per lane: dup_tile_wave_tasks), so compare loads run beside the hashing from
   // the start (dup_tile_of, sd_dup_runs.h).
-  const DupTile tile = dup_tile_of(blockIdx.x, G, TH, dl.tail_tiles);
+  DupTile tile;
+  uint32_t quota = dup_tile_wave_tasks();
+  bool leaves_cu = false;  // (uniform) a compare workgroup that is counted in its CU's slot
+  const bool roles = B == (int)DUP_ROLE_BLOCK && dl.tail_tiles == 0;  // (uniform)
+  if (roles) {
+    // Roles taken at run time (sd_dup_runs.h): lane 0 decides, and the workgroup reads the role
+    // from a stack word that is dead until the hashing starts (hence the second barrier).
+    const uint32_t n_tasks = dup_task_count(n_cand);
+    if (threadIdx.x == 0) {
+      uint32_t role = DUP_ROLE_COMPARE;
+      bool compare = dup_wants_compare(
+          __hip_atomic_load(&dl.counters[DUP_QUEUE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), n_tasks,
+          __hip_atomic_load(&dl.counters[DUP_HASH_QUEUE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), TH);
+      if (compare) {
+        const uint32_t slot = dup_this_cu_slot();
+        compare = dup_cu_has_room(atomicAdd(&dl.cu[slot], 1u)) &&
+                  atomicAdd(&dl.counters[DUP_COMPARE_WGS], 1u) < dup_compare_budget(G, TH);
+        if (!compare) atomicSub(&dl.cu[slot], 1u);
+        stack_lds[0][0][1] = slot;  // a compare workgroup never touches the stack: kept for its exit
+      }
+      if (!compare) {
+        role = atomicAdd(&dl.counters[DUP_HASH_QUEUE], 1u);
+        if (role >= TH) role = DUP_ROLE_DRAIN;  // no hash tile left: the drain fills itself
+      }
+      stack_lds[0][0][0] = role;
+    }
+    __syncthreads();
+    const uint32_t role = (uint32_t)__builtin_amdgcn_readfirstlane((int)stack_lds[0][0][0]);
+    __syncthreads();
+    // (a compare workgroup of a grid that is resident all at once has no quota: sd_dup_runs.h)
+    tile = DupTile{role >= DUP_ROLE_COMPARE, role == DUP_ROLE_DRAIN || !dup_compare_has_quota(G, dl.slots), role};
+    quota = dup_role_wave_tasks();
+    leaves_cu = role == DUP_ROLE_COMPARE;
+  } else {
+    tile = dup_tile_of(blockIdx.x, G, TH, dl.tail_tiles);
+  }
+#if SD_DBG
+  if (threadIdx.x == 0) {
+    if (blockIdx.x == 0) dl.counters[DUP_TILES_WANT] = TH;
+    if (!tile.compare) atomicAdd(&dl.counters[DUP_TILES_RUN], 1u);
+  }
+#endif
   if (blockIdx.x == 0 && threadIdx.x < 2) ro.objects[threadIdx.x] = 0;
   if (blockIdx.x == 0 && threadIdx.x == 0 && dl.note) {
     dl.note[1] = n_cand;
@@ -521,7 +581,7 @@ __device__ __forceinline__ void dup_mixed_kernel_body(const uint8_t* __restrict_
     const uint32_t voff = dup_slice_quad_offset(0, 0, threadIdx.x & 63u);
     const uint32_t n_tasks = dup_task_count(n_cand);
     uint32_t done = 0, refs = 0;
-    for (uint32_t k = 0; tile.tail || k < dup_tile_wave_tasks(); ++k) {
+    for (uint32_t k = 0; tile.tail || k < quota; ++k) {
       uint32_t t = 0;
       if (voff == 0) t = atomicAdd(&dl.counters[DUP_QUEUE], 1u);
       t = __builtin_amdgcn_readfirstlane(t);
@@ -532,6 +592,10 @@ __device__ __forceinline__ void dup_mixed_kernel_body(const uint8_t* __restrict_
     if (voff == 0 && done) {
       atomicAdd(&dl.counters[DUP_TASKS], done);
       atomicAdd(&dl.counters[DUP_REFS], refs);
+    }
+    if (leaves_cu) {  // its CU may hold another compare workgroup
+      __syncthreads();
+      if (threadIdx.x == 0) atomicSub(&dl.cu[stack_lds[0][0][1]], 1u);
     }
   }
 }
@@ -558,6 +622,17 @@ sd_cas_dup_finish_kernel(const uint8_t* __restrict__ content, uint64_t stride,
   constexpr int B = SAMPLED_BLOCK_NARROW;
   __shared__ uint32_t stack_lds[SAMPLED_DEPTH][8][B];
   const uint32_t n_cand = dl.counters[DUP_N_CAND];
+#if SD_DBG
+  // conservation of the main kernel's work, whichever way its workgroups got their roles
+  if (blockIdx.x == 0) {
+    SD_DBG_CHECK(threadIdx.x != 0 || dl.counters[DUP_TILES_RUN] == dl.counters[DUP_TILES_WANT],
+                 "dup roles: %u hash tiles run of %u", dl.counters[DUP_TILES_RUN], dl.counters[DUP_TILES_WANT]);
+    SD_DBG_CHECK(threadIdx.x != 0 || dl.counters[DUP_TASKS] == dup_task_count(n_cand),
+                 "dup roles: %u tasks run of %u", dl.counters[DUP_TASKS], dup_task_count(n_cand));
+    for (uint32_t i = threadIdx.x; i < DUP_CU_SLOTS; i += B)
+      SD_DBG_CHECK(dl.cu[i] == 0, "dup roles: CU slot %u left at %u", i, dl.cu[i]);
+  }
+#endif
   if (blockIdx.x * B >= n_cand) return;  // (uniform)
   const uint32_t i = blockIdx.x * B + threadIdx.x;
   const bool live = i < n_cand;
@@ -718,6 +793,8 @@ sd_cas_packed_kernel(const uint8_t* __restrict__ arena, const uint64_t* __restri
   keys[f] = key_of(cv);
 }
 
+SD_DBG_ACCESSOR(sd_dbg_violations_cas_hash)
+
 }  // namespace sdcas
 
 // ---- host launchers ----------------------------------------------------------------
@@ -811,7 +888,8 @@ DupVerifyWs dup_verify_layout(void* ws, uint64_t n) {
   L.list_h = w.take<uint32_t>(n);  L.list_c = w.take<uint32_t>(n);  L.same = w.take<uint32_t>(n);
   L.cnt = w.take<uint32_t>(n);  L.first = w.take<uint32_t>(n);  L.rank = w.take<uint32_t>(n);
   L.partial = w.take<uint32_t>(n / 4096 + 1);  // exclusive_scan_u32's scratch
-  L.counters = w.take<uint32_t>(DUP_COUNTERS);  L.objects = w.take<uint64_t>(1);
+  L.counters = w.take<uint32_t>(DUP_COUNTERS);  L.cu = w.take<uint32_t>(DUP_CU_SLOTS);
+  L.objects = w.take<uint64_t>(1);
   L.bytes = w.bytes();  return L;
 }
 size_t dup_verify_workspace_bytes(uint64_t n) { return dup_verify_layout(nullptr, n).bytes; }
@@ -826,7 +904,7 @@ hipError_t dup_candidates(const uint8_t* content, uint64_t stride, const uint64_
                           const DupVerifyWs& L, void* group_ws, uint32_t* totals, hipStream_t s) {
   if (n == 0) return hipSuccess;
   sd_dup_probe_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, s>>>(content, stride, sizes, n, L.probes,
-                                                                  L.counters, L.cnt);
+                                                                  L.counters, L.cu, L.cnt);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   return hash_group_min(L.probes, nullptr, n, L.cand, L.objects, group_ws, totals, s);
@@ -837,32 +915,34 @@ hipError_t hash_sampled_regions_verify(const uint8_t* content, uint64_t stride, 
                                        uint32_t* rfile, uint32_t* cursor, uint64_t cap,
                                        uint64_t* spill_keys, uint32_t* spill_file, uint32_t* overflow,
                                        uint64_t* objects, const DupVerifyWs& L, uint32_t* note,
-                                       uint32_t seq, hipStream_t s, uint32_t cus) {
+                                       uint32_t seq, hipStream_t s, uint32_t cus, bool cu_roles) {
   if (n == 0) return hipSuccess;
   const RegionOut ro{rkeys, rfile, cursor, cap, spill_keys, spill_file, rep, overflow,
                      (unsigned long long*)objects};
   const uint64_t blocks = (n + SAMPLED_BLOCK - 1) / SAMPLED_BLOCK;
   const uint64_t quanta = cus ? (n + (uint64_t)cus * 256 - 1) / ((uint64_t)cus * 256) : 0;
-  const bool narrow = cus && (blocks < cus || (quanta & 1));  // the grid choice of hash_sampled
-  // Tail compare tiles: the last round of hash tiles frees the chip's workgroup slots one by
-  // one over a tile's time, half the slots x that time in all, and a compare tile of B pairs
+  // static placement: the grid choice of hash_sampled.  Run-time roles (sd_dup_runs.h): 256-lane
+  // workgroups for every batch shape, so a compare workgroup is one wave on each SIMD of its CU
+  const bool narrow = cu_roles || (cus && (blocks < cus || (quanta & 1)));
+  // Static placement's tail compare tiles: the last round of hash tiles frees the chip's workgroup
+  // slots one by one over a tile's time, half the slots x that time in all, and a compare tile of B pairs
   // took ~0.7 of a hash tile's time beside hash tiles (profiles/dup_verify/): slots / 2 / 0.7.
   // A tile of B entries in runs reads ~0.8 of the rows a tile of B pairs did, which would put
   // the count near 0.9 slots; the sweep on the run kernel (profiles/dup_groups/: 1 / 192 / 365 /
   // 448 / 512 / all 768 tail tiles: 22.55 / 21.3 / 20.9 / 21.15 / 20.75 / 22.55 ms) is flat from
   // 365 to 512 within the process-to-process spread, so 5/7 stays.
   const uint32_t slots = (cus ? cus : 256u) * (narrow ? 4u : 2u);
-  const uint32_t tail_tiles = slots * SD_DUP_TAIL_NUM / SD_DUP_TAIL_DEN;  // (>= 1)
-  const DupLists dl{L.cand, L.list_h, L.list_c, L.same, L.cnt, L.first, L.rank, L.counters,
-                    tail_tiles, note, seq, (uint32_t)n};
+  const uint32_t tail_tiles = cu_roles ? 0u : slots * SD_DUP_TAIL_NUM / SD_DUP_TAIL_DEN;  // (static: >= 1)
+  const DupLists dl{L.cand, L.list_h, L.list_c, L.same, L.cnt, L.first, L.rank, L.counters, L.cu,
+                    tail_tiles, slots, note, seq, (uint32_t)n};
   const uint32_t nb256 = (uint32_t)((n + 255) / 256);
   sd_dup_compact_kernel<<<nb256, 256, 0, s>>>(n, dl);
   hipError_t e = exclusive_scan_u32(L.cnt, L.first, n, L.partial, s);
   if (e != hipSuccess) return e;
   sd_dup_order_kernel<<<nb256, 256, 0, s>>>(n, dl);
   if (narrow) {
-    const uint64_t nb = (n + SAMPLED_BLOCK_NARROW - 1) / SAMPLED_BLOCK_NARROW;
-    sd_cas_dup_mixed_kernel_256<<<(uint32_t)nb + 1, SAMPLED_BLOCK_NARROW, 0, s>>>(content, stride, sizes,
+    static_assert(SAMPLED_BLOCK_NARROW == (int)DUP_ROLE_BLOCK, "dup_role_grid is this grid");
+    sd_cas_dup_mixed_kernel_256<<<dup_role_grid(n), SAMPLED_BLOCK_NARROW, 0, s>>>(content, stride, sizes,
                                                                                  keys, ro, dl);
   } else {
     sd_cas_dup_mixed_kernel<<<(uint32_t)blocks + 1, SAMPLED_BLOCK, 0, s>>>(content, stride, sizes, keys,

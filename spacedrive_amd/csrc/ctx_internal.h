@@ -150,6 +150,8 @@ class HostPool {
 };
 
 constexpr uint32_t DUPV_SKIP_CALLS = 16, DUPV_MIN_CANDIDATE_SHARE = 32;
+// SD_CAS_DUP_PLACEMENT: how the workgroups of the verified chain's main kernel get their work
+enum DupPlacement { DUP_PLACE_STATIC = 0, DUP_PLACE_CU = 1, DUP_PLACE_AUTO = 2 };
 
 struct sd_cas_ctx {
   int device = 0;
@@ -176,7 +178,12 @@ struct sd_cas_ctx {
   int exact_method = 0;  // SD_CAS_EXACT_* (sd_cas_set_exact_method)
   uint64_t exact_mismatched = 0, exact_fallbacks = 0;  // of the last group_exact call
   bool dup_verify = true;
-  uint64_t dupv_n = 0;            // files of the last verified call (0: none, or the setter was off)
+  // SD_CAS_DUP_PLACEMENT=static|cu|auto, read at creation.  static: the tile map fixed before
+  // launch (dup_tile_of); cu: roles taken at run time, at most DUP_CU_LIMIT compare workgroups per
+  // CU (sd_dup_runs.h); auto (the default): cu for a grid of at least DUP_ROLES_MIN_ROUNDS times the
+  // workgroups the chip holds at once (dup_roles_pay), static below
+  DupPlacement dup_placement = DUP_PLACE_AUTO;
+  uint64_t dupv_n = 0;           // files of the last verified call (0: none, or the setter was off)
   hipStream_t dupv_stream = nullptr;
   // Probing a batch costs ~0.3 ms at 1.31 M files whatever it finds, and pays from ~1 candidate
   // in 32 files on.  Each verified call leaves {seq, candidates, files} in pinned host memory

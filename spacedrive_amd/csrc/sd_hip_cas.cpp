@@ -32,6 +32,7 @@
 #include "sd_checksum.h"
 #include "sd_exact_dups.h"
 #include "sd_group.h"
+#include "sd_dup_runs.h"
 #include "sd_kernels.h"
 #include "sd_links.h"
 #include "sd_mix.h"
@@ -44,6 +45,7 @@ using namespace sdcas;
 #if SD_DBG
 namespace sdcas {
 uint32_t sd_dbg_violations_group_hash();
+uint32_t sd_dbg_violations_cas_hash();
 uint32_t sd_dbg_violations_group();
 uint32_t sd_dbg_violations_checksum();
 uint32_t sd_dbg_violations_links();
@@ -56,7 +58,7 @@ uint32_t sd_dbg_violations_exact_dups();
 // ... plus the allocation tails found changed (below)
 #include "ctx_internal.h"
 extern "C" uint64_t sd_cas_debug_violations(void) {
-  return (uint64_t)sd_dbg_violations_group_hash() + sd_dbg_violations_group() +
+  return (uint64_t)sd_dbg_violations_group_hash() + sd_dbg_violations_cas_hash() + sd_dbg_violations_group() +
          sd_dbg_violations_checksum() + sd_dbg_violations_links() + sd_dbg_violations_inplace() +
          sd_dbg_violations_object_stats() + sd_dbg_violations_exact_dups() + sd_dbg_tail_check_all();
 }
@@ -282,6 +284,16 @@ int sd_cas_ctx_create(int device, sd_cas_ctx** out) {
       fprintf(stderr, "sd_hip_cas: SD_CAS_TEST_TABLE_FILL=%u (test knob): the fused grouping's "
               "region tables overflow at %u distinct keys (exact, much slower)\n",
               c->test_table_fill, c->test_table_fill);
+    // the same binary runs either placement of the duplicate compares (A/B, and the fallback)
+    const char* p = getenv("SD_CAS_DUP_PLACEMENT");
+    if (p && *p) {
+      if (strcmp(p, "cu") != 0 && strcmp(p, "static") != 0 && strcmp(p, "auto") != 0) {
+        sd_cas_ctx_destroy(c);
+        g_ctx_create_err = std::string("SD_CAS_DUP_PLACEMENT=") + p + ": static, cu or auto";
+        return SD_CAS_EINVAL;
+      }
+      c->dup_placement = !strcmp(p, "cu") ? DUP_PLACE_CU : !strcmp(p, "static") ? DUP_PLACE_STATIC : DUP_PLACE_AUTO;
+    }
   }
   bind_pool_to_gpu_node(c);
   // the pool's readers on private descriptor tables (HostPool::set_private_fds)
@@ -618,6 +630,9 @@ int sd_cas_hash_regions_sampled_dev(sd_cas_ctx* c, const void* d_content, uint64
     if (c->dupv_n && c->dupv_stream != s && c->region_cur >= 0)
       HIP_TRY(c, hipStreamWaitEvent(s, c->region_hashed[c->region_cur], 0));
     const DupVerifyWs D = dup_verify_layout(c->dupv.p, n);
+    const uint32_t cus = (uint32_t)(c->quantum / 256);
+    const bool cu_roles = c->dup_placement == DUP_PLACE_CU ||
+                          (c->dup_placement == DUP_PLACE_AUTO && dup_roles_pay(dup_role_grid(n), 4 * cus));
     HIP_TRY(c, sd_ws_acquire(c, s));  // the probes' grouping runs in ws / gtotals
     e = dup_candidates((const uint8_t*)d_content, stride, d_sizes, n, D, c->ws.p, c->gtotals, s);
     HIP_TRY(c, sd_ws_release(c, s));
@@ -625,7 +640,7 @@ int sd_cas_hash_regions_sampled_dev(sd_cas_ctx* c, const void* d_content, uint64
       e = hash_sampled_regions_verify((const uint8_t*)d_content, stride, d_sizes, n, d_keys, d_rep,
                                       L.rkeys, L.rfile, cur, region_capacity(n), L.spill_keys,
                                       L.spill_file, d_overflow, L.objects, D, c->dupv_note,
-                                      ++c->dupv_seq, s, (uint32_t)(c->quantum / 256));
+                                      ++c->dupv_seq, s, cus, cu_roles);
     c->dupv_n = e == hipSuccess ? n : 0;
     c->dupv_stream = s;
   } else {

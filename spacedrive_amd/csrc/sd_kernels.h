@@ -42,14 +42,18 @@ hipError_t hash_sampled_regions(const uint8_t* content, uint64_t stride, const u
 // holds the probes, cand (the smallest file with the same probe), the hash and candidate lists,
 // the verified flags, the arrays that order the candidates by original (cnt, first, rank, the
 // scan's partial sums) and counters[DUP_COUNTERS]: files to hash, candidates, verified, rehashed,
-// the task queue, groups, tasks, reference rows read.
+// the task queue, groups, tasks, reference rows read, and the run-time roles' words (the hash-tile
+// queue, compare workgroups started; debug library: hash tiles run and wanted), and cu[DUP_CU_SLOTS],
+// the compare workgroups resident per CU (sd_dup_runs.h), zeroed with the counters.
 // dup_candidates fills probes and cand (the hash grouping: group_ws, totals as hash_group_min);
 // hash_sampled_regions_verify is the rest of the chain and needs neither.  note (pinned host
 // memory, 3 u32, or nullptr): the mixed kernel stores {seq, candidates, n} there, seq last, so
-// the host can see without a sync how many candidates an earlier call found.
-constexpr uint32_t DUP_COUNTERS = 8;
+// the host can see without a sync how many candidates an earlier call found.  cu_roles: the main
+// kernel's workgroups take their roles at run time (SD_CAS_DUP_PLACEMENT=cu) instead of from the
+// static tile map.
+constexpr uint32_t DUP_COUNTERS = 16;
 struct DupVerifyWs {
-  uint64_t* probes; uint32_t *cand, *list_h, *list_c, *same, *cnt, *first, *rank, *partial, *counters;
+  uint64_t* probes; uint32_t *cand, *list_h, *list_c, *same, *cnt, *first, *rank, *partial, *counters, *cu;
   uint64_t* objects; size_t bytes;
 };
 DupVerifyWs dup_verify_layout(void* ws, uint64_t n);  // ws == nullptr: measure only (sd_ws.h)
@@ -61,7 +65,7 @@ hipError_t hash_sampled_regions_verify(const uint8_t* content, uint64_t stride, 
                                        uint32_t* rfile, uint32_t* cursor, uint64_t cap,
                                        uint64_t* spill_keys, uint32_t* spill_file, uint32_t* overflow,
                                        uint64_t* objects, const DupVerifyWs& L, uint32_t* note,
-                                       uint32_t seq, hipStream_t s, uint32_t cus);
+                                       uint32_t seq, hipStream_t s, uint32_t cus, bool cu_roles);
 // pinned host -> device copy by a kernel (16-B aligned; else hipMemcpyAsync)
 hipError_t pull_host(void* dst, const void* src, uint64_t bytes, hipStream_t s);
 hipError_t hash_packed(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,
