@@ -531,6 +531,44 @@ int sd_cas_set_exact_method(sd_cas_ctx* ctx, int method);
 /* Of the context's last sd_cas_group_exact_dev call: the rows whose fast-path head did not match
  * them (0 under WORDS), and 1 if the word-wise path ran, else 0. */
 int sd_cas_group_exact_counters(sd_cas_ctx* ctx, uint64_t* out_mismatched_rows, uint64_t* out_fallbacks);
+/* The same split without digests: the members of a candidate set are compared with each other,
+ * whole content against whole content, where they lie in HBM.
+ *   d_rep_exact[i] = min{ j : class[j] == class[i] && content j == content i },
+ *   class[i] = (d_rep[i] as a VALUE, d_lens[i]),
+ * content i = d_arena + d_offs[i], d_lens[i] bytes, under the arena layout's rules of
+ * sd_cas_checksums_dev: 16-B aligned offsets (and arena), lengths <= 64 GiB, every end within
+ * arena_bytes, readable to the 16-B round-up of its end (the padding may differ between equal
+ * contents: it is masked out).  The bounds are checked on the device first and the call waits for
+ * that verdict: on a violation SD_CAS_EINVAL, nothing is read and d_rep_exact is not written.
+ * d_rep is never used as an index (any u32 is safe) and need not be canonical; NULL, n > 2^24 or
+ * d_rep_exact overlapping d_rep is SD_CAS_EINVAL; n == 0 launches nothing.  *out_objects (may be
+ * NULL) = the rows with rep_exact[i] == i, after the call also the context's "last grouping"
+ * Object count.  Blocking (one small read-back per round).
+ * What is read: rows of one rep with different lengths split without a byte being read, a class of
+ * one row is never read, a length-0 content is never read.  Otherwise rounds: each unresolved row
+ * is compared with its pivot (at first its class's first row) in 64-KiB pieces, a row refuted in
+ * one piece is not read in the next; an equal row joins its pivot, and the smallest unequal row of
+ * a pivot becomes a head and the pivot of the others.  A class of d distinct contents takes d - 1
+ * or d rounds and reads each of its rows up to d - 1 times: m pairwise-distinct members of one
+ * class cost m rounds and O(m^2) compares.  After max_rounds rounds (0 = no cap) the rows still
+ * unresolved, with their pivots, are finished by sd_cas_checksums_dev + sd_cas_group_exact_dev
+ * (this call then also replaces sd_cas_group_exact_counters' values); results are identical for
+ * every max_rounds.  The default comes from the sweep of tools/bench_exact_compare.py
+ * (profiles/exact_compare/rounds_sweep.txt: classes of d distinct contents, four rows each): up to
+ * d = 3 comparing to the end was faster than any capped call, from d = 4 on finishing by digest
+ * after the first round was faster than comparing to the end, so a class that needs a fourth
+ * round is handed over. */
+#define SD_CAS_EXACT_COMPARE_ROUNDS_DEFAULT 3
+int sd_cas_group_exact_contents_dev(sd_cas_ctx* ctx, const uint32_t* d_rep, const void* d_arena,
+                                    uint64_t arena_bytes, const uint64_t* d_offs, const uint64_t* d_lens,
+                                    size_t n, uint32_t* d_rep_exact, uint64_t* out_objects, void* stream);
+int sd_cas_set_exact_compare_rounds(sd_cas_ctx* ctx, uint32_t max_rounds);
+/* Of the context's last sd_cas_group_exact_contents_dev call: compare launches (0 when no class
+ * has two rows), row-against-pivot comparisons started (rows split by length alone are not among
+ * them), those that found a difference, and the unresolved rows handed to the digest route (their
+ * pivots, which go with them, not counted). */
+int sd_cas_exact_compare_counters(sd_cas_ctx* ctx, uint64_t* out_rounds, uint64_t* out_compares,
+                                  uint64_t* out_unequal, uint64_t* out_digest_rows);
 /* A checksum string (Hash::to_hex of hash.rs:24) <-> its 32 bytes.  from_hex takes exactly 64 hex
  * digits of either case followed by a NUL, anything else is SD_CAS_EINVAL and `out` is left as it
  * was; to_hex writes 64 lowercase digits and a NUL. */

@@ -191,6 +191,13 @@ extern "C" {
     pub fn sd_cas_set_exact_method(ctx: *mut sd_cas_ctx, method: c_int) -> c_int;
     pub fn sd_cas_group_exact_counters(ctx: *mut sd_cas_ctx, out_mismatched_rows: *mut u64,
                                        out_fallbacks: *mut u64) -> c_int;
+    pub fn sd_cas_group_exact_contents_dev(ctx: *mut sd_cas_ctx, d_rep: *const u32, d_arena: *const c_void,
+                                           arena_bytes: u64, d_offs: *const u64, d_lens: *const u64,
+                                           n: usize, d_rep_exact: *mut u32, out_objects: *mut u64,
+                                           stream: *mut c_void) -> c_int;
+    pub fn sd_cas_set_exact_compare_rounds(ctx: *mut sd_cas_ctx, max_rounds: u32) -> c_int;
+    pub fn sd_cas_exact_compare_counters(ctx: *mut sd_cas_ctx, out_rounds: *mut u64, out_compares: *mut u64,
+                                         out_unequal: *mut u64, out_digest_rows: *mut u64) -> c_int;
     pub fn sd_cas_digest_from_hex(hex: *const c_char, out: *mut u8) -> c_int;
     pub fn sd_cas_digest_to_hex(digest: *const u8, out: *mut c_char);
     pub fn sd_cas_duplicate_report_exact(ctx: *mut sd_cas_ctx, h_keys: *const u64, h_sizes: *const u64,

@@ -82,6 +82,9 @@ SIGNATURES = [
     ("sd_cas_group_exact_dev", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("sd_cas_set_exact_method", _i, [_vp, _i]),
     ("sd_cas_group_exact_counters", _i, [_vp, _vp, _vp]),
+    ("sd_cas_group_exact_contents_dev", _i, [_vp, _vp, _vp, _u64, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("sd_cas_set_exact_compare_rounds", _i, [_vp, _u32]),
+    ("sd_cas_exact_compare_counters", _i, [_vp, _vp, _vp, _vp, _vp]),
     ("sd_cas_digest_from_hex", _i, [_cp, _vp]),
     ("sd_cas_digest_to_hex", None, [_vp, _cp]),
     ("sd_cas_duplicate_report_exact", _i,

@@ -46,6 +46,7 @@ STAT_NAMES = ("rows", "objects", "total_bytes", "unique_bytes", "duplicate_sets"
 TOP_MAX = 65536
 TOP_TILE = 16384
 EXACT_AUTO, EXACT_WORDS = 0, 1  # SD_CAS_EXACT_*
+EXACT_COMPARE_ROUNDS_DEFAULT = 3  # SD_CAS_EXACT_COMPARE_ROUNDS_DEFAULT
 
 
 def key_to_cas_id(key: int) -> str:
@@ -179,6 +180,21 @@ class ExactDuplicateReport:
     unconfirmed: int
     top_heads: np.ndarray
     top_waste: np.ndarray
+
+
+@dataclass
+class ComparedDuplicateReport(ExactDuplicateReport):
+    """CasEngine.exact_duplicates_compared: ExactDuplicateReport's fields, the exact ones found
+    by comparing the members of each sampled set with each other (unconfirmed = candidates
+    whose read failed or whose length changed since the stat), plus what the route read:
+    candidate_rows / candidate_bytes = the hashed rows with a sampled copy and their sizes (no
+    other file's whole content is opened), compared_rows = the rows that went through
+    group_exact_contents, checksum_rows = the rows of sets too large for one arena, which took
+    file_checksums and the digest split."""
+    candidate_rows: int = 0
+    candidate_bytes: int = 0
+    compared_rows: int = 0
+    checksum_rows: int = 0
 
 
 class CasEngine:
@@ -738,6 +754,169 @@ class CasEngine:
         keys, cas_status, sizes, digests, _ = self.identify_validate(paths)
         state = np.where(cas_status == 0, 0, np.where(cas_status == STATUS_NO_CAS, 1, 2)).astype(np.uint8)
         return self.duplicate_report_exact(keys, sizes, digests, state, k)
+
+    def set_exact_compare_rounds(self, max_rounds: Optional[int] = None) -> None:
+        """group_exact_contents' round cap: after max_rounds compare rounds the rows still
+        unresolved are finished by checksums_dev + group_exact (0 = no cap, None = the library's
+        default).  Identical results for every value."""
+        if max_rounds is None:
+            max_rounds = EXACT_COMPARE_ROUNDS_DEFAULT
+        if not 0 <= int(max_rounds) < 1 << 32:
+            raise ValueError(f"max_rounds {max_rounds} outside [0, 2^32)")
+        self._check(self.L.sd_cas_set_exact_compare_rounds(self.h, int(max_rounds)), "set_exact_compare_rounds")
+
+    def group_exact_contents(self, rep, arena, offs, lens, rep_exact, arena_bytes: Optional[int] = None,
+                             stream: Optional[int] = None) -> int:
+        """sd_cas_group_exact_contents_dev: rep_exact[i] = the first row with row i's rep (a
+        value), length AND bytes, found by comparing contents, not by hashing them.  Content i =
+        arena[offs[i] : offs[i] + lens[i]] as for checksums_dev (int64 tensors, 16-B aligned
+        offsets, readable to the 16-B round-up); rep / rep_exact int32 [n] device tensors.
+        Blocking; returns the number of rows with rep_exact[i] == i.  Raises CasError (EINVAL)
+        when a content breaks the bounds; rep_exact is then untouched."""
+        import torch
+        n = int(rep_exact.numel())
+        _check_dev(rep_exact, (torch.int32, torch.uint32), n, "rep_exact")
+        _check_dev(rep, (torch.int32, torch.uint32), n, "rep")
+        _check_dev(offs, (torch.int64, torch.uint64), n, "offs")
+        _check_dev(lens, (torch.int64, torch.uint64), n, "lens")
+        if not arena.is_cuda or not arena.is_contiguous():
+            raise ValueError("arena: expected a contiguous CUDA tensor")
+        ab = int(arena.numel() * arena.element_size()) if arena_bytes is None else int(arena_bytes)
+        obj = ctypes.c_uint64(0)
+        self._check(self.L.sd_cas_group_exact_contents_dev(
+            self.h, _ptr(rep), _ptr(arena), ab, _ptr(offs), _ptr(lens), n, _ptr(rep_exact),
+            ctypes.byref(obj), _stream(stream)), "group_exact_contents")
+        return int(obj.value)
+
+    def exact_compare_counters(self) -> tuple[int, int, int, int]:
+        """(rounds, compares, unequal, digest_rows) of the last group_exact_contents call."""
+        v = [ctypes.c_uint64(0) for _ in range(4)]
+        self._check(self.L.sd_cas_exact_compare_counters(self.h, *[ctypes.byref(x) for x in v]),
+                    "exact_compare_counters")
+        return tuple(int(x.value) for x in v)
+
+    def exact_duplicates_compared(self, paths: Sequence[str], k: int = 0,
+                                  arena_bytes: Optional[int] = None) -> ComparedDuplicateReport:
+        """exact_duplicates without reading what cannot be a duplicate and without digests:
+        size, then the sampled cas_id (at most 57,344 B of a file over 100 KiB), then the whole
+        content of the CANDIDATES only, the hashed rows whose sampled set has two members, which
+        are compared with each other on the device (group_exact_contents).  Every other hashed
+        row is its own exact Object and is not opened again.  Whole sets are packed in ascending
+        row order into a device arena of at most arena_bytes (default: half of the free device
+        memory torch reports at the call, a choice); a set that does not fit takes file_checksums
+        and the digest split.  On files that do not change, every field shared with
+        exact_duplicates(paths, k) equals that call's."""
+        import torch
+        from concurrent.futures import ThreadPoolExecutor
+        n, k = len(paths), int(k)
+        keys, cas_status, sizes = self.file_metadata_from_paths(paths)
+        state = np.where(cas_status == 0, 0, np.where(cas_status == STATUS_NO_CAS, 1, 2)).astype(np.uint8)
+        sampled = self.duplicate_report(keys, sizes, state, k=0)
+        hashed = state == 0
+        rows_all = np.arange(n, dtype=np.uint32)
+        rep_exact = np.where(hashed, rows_all, np.uint32(NO_OBJECT)).astype(np.uint32)
+        unconfirmed = np.zeros(n, dtype=bool)
+        cand = np.flatnonzero(hashed & (sampled.copies >= 2))
+        if arena_bytes is None:
+            arena_bytes = int(torch.cuda.mem_get_info()[0]) // 2 if len(cand) else 0
+        arena_bytes = int(arena_bytes)
+        room = (sizes.astype(np.int64) + 15) & ~np.int64(15)  # a content's room in the arena
+        # the sampled sets in ascending order of their first row; a set's rows ascend as well
+        by_set = cand[np.argsort(sampled.rep[cand], kind="stable")]
+        cuts = np.flatnonzero(np.diff(sampled.rep[by_set])) + 1
+        batches, batch, used, big = [], [], 0, []
+        for members in np.split(by_set, cuts) if len(by_set) else []:
+            need = int(room[members].sum())
+            if need > arena_bytes:
+                big.append(members)
+                continue
+            if used + need > arena_bytes:
+                batches.append(batch)
+                batch, used = [], 0
+            batch.append(members)
+            used += need
+        if batch:
+            batches.append(batch)
+        compared_rows = checksum_rows = 0
+
+        def split_on_device(rows, fn):
+            """rows ascending; fn(rep, out) runs a grouping over them: back to the caller's numbering"""
+            rep_t = torch.from_numpy(sampled.rep[rows].view(np.int32)).cuda()
+            out = torch.empty(len(rows), dtype=torch.int32, device="cuda")
+            fn(rep_t, out)
+            rep_exact[rows] = rows[out.cpu().numpy().view(np.uint32)]
+
+        if batches:
+            cap = max(sum(int(room[m].sum()) for m in b) for b in batches)
+            staging = self.alloc_pinned(max(cap, 16))
+            try:
+                with ThreadPoolExecutor(max_workers=16) as pool:  # (never sized by the machine's CPUs)
+                    for b in batches:
+                        rows = np.sort(np.concatenate(b)).astype(np.uint32)
+                        offs = np.concatenate([[0], np.cumsum(room[rows])[:-1]]).astype(np.int64)
+
+                        def read(j):
+                            want, at = int(sizes[rows[j]]), int(offs[j])
+                            try:
+                                with open(paths[rows[j]], "rb", buffering=0) as fh:
+                                    got, view = 0, memoryview(staging)[at:at + want]
+                                    while got < want:
+                                        r = fh.readinto(view[got:])
+                                        if not r:
+                                            return False
+                                        got += r
+                                    return fh.read(1) == b""  # still sizes[i] bytes long
+                            except OSError:
+                                return False
+                        ok = np.fromiter(pool.map(read, range(len(rows))), dtype=bool, count=len(rows))
+                        unconfirmed[rows[~ok]] = True
+                        total = int(room[rows].sum())
+                        arena = torch.empty(max(total, 16), dtype=torch.uint8, device="cuda")
+                        arena[:total].copy_(torch.from_numpy(staging[:total]))
+                        rows, offs = rows[ok], offs[ok]
+                        if len(rows):
+                            d_offs = torch.from_numpy(offs).cuda()
+                            d_lens = torch.from_numpy(sizes[rows].astype(np.int64)).cuda()
+                            split_on_device(rows, lambda r, o: self.group_exact_contents(
+                                r, arena, d_offs, d_lens, o, arena_bytes=total))
+                            compared_rows += len(rows)
+                        del arena
+            finally:
+                self.free_pinned(staging)
+        for members in big:  # the route exact_duplicates takes, for these rows alone
+            rows = np.sort(members).astype(np.uint32)
+            checksum_rows += len(rows)
+            digests, _ = self.file_checksums([paths[i] for i in rows])
+            ok = np.array([d is not None for d in digests], dtype=bool)
+            unconfirmed[rows[~ok]] = True
+            rows = rows[ok]
+            if len(rows):
+                raw = np.frombuffer(b"".join(bytes.fromhex(d) for d in digests if d is not None), dtype=np.uint8)
+                d_dig = torch.from_numpy(raw.copy()).cuda()
+                split_on_device(rows, lambda r, o: self.group_exact(r, d_dig, o))
+        rep_exact[unconfirmed] = NO_OBJECT
+        # copies, totals and the top list over the eligible rows, compacted and scattered back
+        elig = np.flatnonzero(hashed & ~unconfirmed).astype(np.uint32)
+        copies = np.zeros(n, dtype=np.uint32)
+        totals_exact = {q: 0 for q in STAT_NAMES}
+        heads = np.full(k, NO_OBJECT, dtype=np.uint32)
+        waste = np.zeros(k, dtype=np.uint64)
+        if len(elig):
+            rep_c = torch.from_numpy(np.searchsorted(elig, rep_exact[elig]).astype(np.int32)).cuda()
+            sizes_c = torch.from_numpy(sizes[elig].astype(np.int64)).cuda()
+            copies_c = torch.zeros(len(elig), dtype=torch.int32, device="cuda")
+            totals_exact = self.object_stats(rep_c, sizes_c, copies_c)
+            copies[elig] = copies_c.cpu().numpy().view(np.uint32)
+            if k:
+                d_heads = torch.empty(k, dtype=torch.int32, device="cuda")
+                d_waste = torch.empty(k, dtype=torch.int64, device="cuda")
+                found = self.top_duplicates(rep_c, sizes_c, copies_c, k, d_heads, d_waste)
+                heads[:found] = elig[d_heads.cpu().numpy().view(np.uint32)[:found]]
+                waste[:found] = d_waste.cpu().numpy().view(np.uint64)[:found]
+        return ComparedDuplicateReport(
+            sampled.rep, rep_exact, copies, sampled.totals, totals_exact, int(unconfirmed.sum()), heads, waste,
+            candidate_rows=len(cand), candidate_bytes=int(sizes[cand].sum()), compared_rows=compared_rows,
+            checksum_rows=checksum_rows)
 
     def keys_to_hex(self, keys, out, stream: Optional[int] = None) -> None:
         """The cas_id column of a device batch: out (uint8, 16 per key, 16-B aligned)."""

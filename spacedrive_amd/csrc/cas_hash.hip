@@ -25,6 +25,7 @@
 
 #include "blake3_lane.hpp"
 #include "blake3_tree.hpp"
+#include "dup_slice.hpp"
 #include "sd_debug.h"
 #include "sd_dup_probe.h"
 #include "sd_dup_runs.h"
@@ -403,7 +404,7 @@ sd_dup_order_kernel(uint64_t n, DupLists dl) {
 // A lane is known by its byte offset in a 1-KiB load (voff = 16 lane) alone, and the lane number
 // is derived from it afresh where a task needs it (dup_lane_of: opaque to the optimizer, which
 // would otherwise keep both in registers over the loop and take the kernel past K1G's 101 VGPRs).
-struct DupSlice { uint4 q[DUP_SLICE_QUADS]; };
+// (DupSlice, dup_slices_differ and dup_first_bit: dup_slice.hpp)
 // row is wave-uniform.  The loads go through a buffer descriptor of the row's 57,344 bytes: a
 // lane's address is its one 32-bit offset, each quad's offset in the row is scalar, and the
 // hardware bounds every load to the row.
@@ -422,20 +423,10 @@ __device__ __forceinline__ void dup_load_slice(DupSlice& d, const uint8_t* __res
     d.q[u] = make_uint4(v.x, v.y, v.z, v.w);
   }
 }
-__device__ __forceinline__ bool dup_slices_differ(const DupSlice& a, const DupSlice& b) {
-  uint32_t d = 0;
-#pragma unroll
-  for (uint32_t u = 0; u < DUP_SLICE_QUADS; ++u)
-    d |= (a.q[u].x ^ b.q[u].x) | (a.q[u].y ^ b.q[u].y) | (a.q[u].z ^ b.q[u].z) | (a.q[u].w ^ b.q[u].w);
-  return __builtin_amdgcn_ballot_w64(d != 0) != 0;  // (wave-uniform)
-}
 __device__ __forceinline__ uint32_t dup_lane_of(uint32_t voff) {
   uint32_t lane;
   asm volatile("v_lshrrev_b32 %0, 4, %1" : "=v"(lane) : "v"(voff));
   return lane;
-}
-__device__ __forceinline__ uint32_t dup_first_bit(uint32_t m) {  // m != 0, uniform
-  return (uint32_t)__builtin_amdgcn_readfirstlane(__builtin_ctz(m));
 }
 
 __device__ __forceinline__ uint32_t dup_compare_task(const uint8_t* __restrict__ content, uint64_t stride,

@@ -177,6 +177,12 @@ struct sd_cas_ctx {
   DevBuf exact;
   int exact_method = 0;  // SD_CAS_EXACT_* (sd_cas_set_exact_method)
   uint64_t exact_mismatched = 0, exact_fallbacks = 0;  // of the last group_exact call
+  // the whole-content compare (sd_cas_group_exact_contents_dev): entry lists, flags, slots, task
+  // tables and the digest finish's compacted rows, beside ws and exact (which its inner groupings,
+  // sorts and digest finish use); ordered across streams like ws
+  DevBuf contents;
+  uint32_t compare_max_rounds = SD_CAS_EXACT_COMPARE_ROUNDS_DEFAULT;  // 0: no cap
+  uint64_t compare_rounds = 0, compare_compares = 0, compare_unequal = 0, compare_digest_rows = 0;
   bool dup_verify = true;
   // SD_CAS_DUP_PLACEMENT=static|cu|auto, read at creation.  static: the tile map fixed before
   // launch (dup_tile_of); cu: roles taken at run time, at most DUP_CU_LIMIT compare workgroups per
@@ -355,6 +361,7 @@ inline const char* sd_buf_name(const sd_cas_ctx* c, const DevBuf& b) {
   return &b == &c->ws ? "ws" : &b == &c->staging ? "staging" : &b == &c->small ? "small"
        : &b == &c->io ? "io" : &b == &c->inplace ? "inplace" : &b == &c->cvbuf ? "cvbuf" : &b == &c->dupv ? "dupv"
        : &b == &c->exact ? "exact"
+       : &b == &c->contents ? "contents"
        : &b == &c->regions[0] ? "regions[0]" : &b == &c->regions[1] ? "regions[1]" : "multi";
 }
 

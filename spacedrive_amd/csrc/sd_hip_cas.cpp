@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "sd_checksum.h"
+#include "sd_content_compare.h"
 #include "sd_exact_dups.h"
 #include "sd_group.h"
 #include "sd_dup_runs.h"
@@ -52,6 +53,7 @@ uint32_t sd_dbg_violations_links();
 uint32_t sd_dbg_violations_inplace();
 uint32_t sd_dbg_violations_object_stats();
 uint32_t sd_dbg_violations_exact_dups();
+uint32_t sd_dbg_violations_content_compare();
 }  // namespace sdcas
 // debug library only (libsd_hip_cas_debug.so, not in the ABI header): invariant violations
 // counted by the device checks of sd_debug.h since the library was loaded
@@ -60,7 +62,8 @@ uint32_t sd_dbg_violations_exact_dups();
 extern "C" uint64_t sd_cas_debug_violations(void) {
   return (uint64_t)sd_dbg_violations_group_hash() + sd_dbg_violations_cas_hash() + sd_dbg_violations_group() +
          sd_dbg_violations_checksum() + sd_dbg_violations_links() + sd_dbg_violations_inplace() +
-         sd_dbg_violations_object_stats() + sd_dbg_violations_exact_dups() + sd_dbg_tail_check_all();
+         sd_dbg_violations_object_stats() + sd_dbg_violations_exact_dups() +
+         sd_dbg_violations_content_compare() + sd_dbg_tail_check_all();
 }
 
 // The allocation tails of ctx_internal.h: every device buffer of a context is followed by
@@ -347,6 +350,7 @@ void sd_cas_ctx_destroy(sd_cas_ctx* c) {
   if (c->inplace.p) (void)sd_dev_free(c->inplace.p);
   if (c->dupv.p) (void)sd_dev_free(c->dupv.p);
   if (c->exact.p) (void)sd_dev_free(c->exact.p);
+  if (c->contents.p) (void)sd_dev_free(c->contents.p);
   if (c->dupv_note) (void)hipHostFree(c->dupv_note);
   if (c->d_scalar) (void)sd_dev_free(c->d_scalar);
   if (c->gtotals) (void)sd_dev_free(c->gtotals);
@@ -1405,6 +1409,147 @@ int sd_cas_group_exact_dev(sd_cas_ctx* c, const uint32_t* d_rep, const uint8_t* 
     HIP_TRY(c, hipStreamSynchronize(s));
   }
   HIP_TRY(c, sd_ws_release(c, s));
+  if (out_objects) *out_objects = objects;
+  return SD_CAS_OK;
+}
+
+// ---- exact duplicate sets by comparison (content_compare.hip) -------------------------------
+
+// c->contents: the class grouping | the two entry lists | flags and slots | the task tables | the
+// counters | the digest finish's rows
+ContentCompareWs sd_content_compare_layout(void* base, size_t n) {
+  WsCarve w(base);  ContentCompareWs L;
+  const uint64_t n_win = ct_window_count((uint32_t)n);
+  L.keys = w.take<uint64_t>(n);  L.ids = w.take<uint32_t>(n);  L.cls = w.take<uint32_t>(n);
+  L.ekey_in = w.take<uint64_t>(n);  L.ekey = w.take<uint64_t>(n);
+  L.erow_in = w.take<uint32_t>(n);  L.erow = w.take<uint32_t>(n);
+  L.neq = w.take<uint32_t>(n);  L.slot = w.take<uint32_t>(n);
+  L.wpieces = w.take<uint32_t>(n_win);  L.wstart = w.take<uint32_t>(n_win);
+  L.scan = w.take<uint32_t>(n_win / 4096 + 1);  // exclusive_scan_u32's scratch
+  L.tasks = w.take<unsigned long long>(1);  L.counters = w.take<uint32_t>(CT_COUNTERS);
+  L.pval = w.take<uint32_t>(n);  L.order = w.take<uint32_t>(n);  L.cpiv = w.take<uint32_t>(n);
+  L.crep = w.take<uint32_t>(n);  L.coffs = w.take<uint64_t>(n);  L.clens = w.take<uint64_t>(n);
+  L.skeys = w.take<uint64_t>(n);  L.cdig = w.take<uint8_t>(32 * (uint64_t)n);
+  L.bytes = w.bytes();  return L;
+}
+
+// the task arithmetic's constants, for tests that place their boundaries from them (internal,
+// like the layouts above): slice, piece, entries per task, default round cap
+extern "C" void sd_content_tasks_constants(uint64_t out[4]) {
+  out[0] = CT_SLICE_BYTES;  out[1] = CT_PIECE_BYTES;  out[2] = CT_RUN_K;
+  out[3] = SD_CAS_EXACT_COMPARE_ROUNDS_DEFAULT;
+}
+
+int sd_cas_set_exact_compare_rounds(sd_cas_ctx* c, uint32_t max_rounds) {
+  if (!c) return SD_CAS_EINVAL;
+  c->compare_max_rounds = max_rounds;
+  return SD_CAS_OK;
+}
+
+int sd_cas_exact_compare_counters(sd_cas_ctx* c, uint64_t* out_rounds, uint64_t* out_compares,
+                                  uint64_t* out_unequal, uint64_t* out_digest_rows) {
+  if (!c || !out_rounds || !out_compares || !out_unequal || !out_digest_rows) return SD_CAS_EINVAL;
+  *out_rounds = c->compare_rounds;
+  *out_compares = c->compare_compares;
+  *out_unequal = c->compare_unequal;
+  *out_digest_rows = c->compare_digest_rows;
+  return SD_CAS_OK;
+}
+
+// The digest finish: the m live entries of the sorted list and their pivots, compacted in row
+// order (a stable one-bit sort of the marks), through the checksum chain and the digest split with
+// rep = the current pivot; a pivot row carries itself, so rows equal to it join it and it stays the
+// smallest of its set.
+static int compare_finish_by_digest(sd_cas_ctx* c, const uint8_t* arena, uint64_t arena_bytes,
+                                    const uint64_t* d_offs, const uint64_t* d_lens, size_t n, uint32_t m,
+                                    const ContentCompareWs& L, uint32_t* d_rep_exact, hipStream_t s) {
+  int rc;
+  uint32_t marked = 0;
+  HIP_TRY(c, ct_mark(L, m, n, s));
+  if ((rc = sd_cas_sort_pairs_dev(c, L.skeys, nullptr, n, L.keys, L.order, 0, 1, s))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(&marked, L.counters + CT_MARKED, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  HIP_TRY(c, ct_gather(L, d_offs, d_lens, marked, s));
+  if ((rc = sd_cas_checksums_dev(c, arena, arena_bytes, L.coffs, L.clens, marked, L.cdig, s))) return rc;
+  if ((rc = sd_cas_group_exact_dev(c, L.cpiv, L.cdig, marked, L.crep, nullptr, s))) return rc;
+  HIP_TRY(c, exact_scatter(L.crep, L.order, marked, d_rep_exact, s));
+  return SD_CAS_OK;
+}
+
+int sd_cas_group_exact_contents_dev(sd_cas_ctx* c, const uint32_t* d_rep, const void* d_arena,
+                                    uint64_t arena_bytes, const uint64_t* d_offs, const uint64_t* d_lens,
+                                    size_t n, uint32_t* d_rep_exact, uint64_t* out_objects, void* stream) {
+  if (!c) return SD_CAS_EINVAL;
+  if (n > CT_MAX_ROWS || (n && (!d_rep || !d_arena || !d_offs || !d_lens || !d_rep_exact)) ||
+      ((uintptr_t)d_arena & 15))
+    return fail(c, SD_CAS_EINVAL, "group_exact_contents: bad arguments");
+  if (n && (uintptr_t)d_rep < (uintptr_t)d_rep_exact + 4 * n && (uintptr_t)d_rep_exact < (uintptr_t)d_rep + 4 * n)
+    return fail(c, SD_CAS_EINVAL, "group_exact_contents: rep_exact aliases rep");
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  c->compare_rounds = c->compare_compares = c->compare_unequal = c->compare_digest_rows = 0;
+  if (n == 0) {  // no Objects: the context's count is 0 (a memset, no launch)
+    HIP_TRY(c, sd_ws_acquire(c, s));
+    HIP_TRY(c, hipMemsetAsync(c->d_scalar, 0, 8, s));
+    HIP_TRY(c, sd_ws_release(c, s));
+    c->region_obj_set = -1;
+    if (out_objects) *out_objects = 0;
+    return SD_CAS_OK;
+  }
+  int rc = ensure(c, c->contents, sd_content_compare_layout(nullptr, n).bytes);
+  if (rc) return rc;
+  const ContentCompareWs L = sd_content_compare_layout(c->contents.p, n);
+  const uint8_t* arena = (const uint8_t*)d_arena;
+  HIP_TRY(c, sd_ws_acquire(c, s));  // c->contents is ordered with ws: the inner calls use both
+  // the bounds verdict first: a batch that breaks them is not read and writes nothing
+  uint32_t bad = 0;
+  HIP_TRY(c, ct_check_bounds(arena_bytes, d_offs, d_lens, n, L.counters, s));
+  HIP_TRY(c, hipMemcpyAsync(&bad, L.counters + CT_BAD, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  if (bad) {
+    (void)sd_ws_release(c, s);
+    return fail(c, SD_CAS_EINVAL, "group_exact_contents: %s",
+                (bad & 1) ? "a content is longer than 64 GiB" : "a content is misaligned or extends past arena_bytes");
+  }
+  // classes: (rep value, length) -> the first row, by the context's grouping; rows of one rep with
+  // different lengths split here, without a byte being read
+  uint64_t classes = 0;
+  if ((rc = sd_cas_group_dev(c, d_lens, n, L.ids, nullptr, s))) return rc;
+  HIP_TRY(c, exact_pair_keys(d_rep, L.ids, n, L.keys, s));
+  if ((rc = sd_cas_group_dev(c, L.keys, n, L.cls, &classes, s))) return rc;
+  HIP_TRY(c, ct_first_entries(L.cls, n, d_rep_exact, L.ekey_in, L.erow_in, L.neq, s));
+  int key_bits = 1;
+  while (((uint64_t)1 << key_bits) <= n) ++key_bits;  // keys are pivots < n, or n
+  const uint32_t grid = (uint32_t)std::max<size_t>(1, c->quantum / 64);  // four workgroups per CU
+  uint32_t listed = (uint32_t)n, live = (uint32_t)(n - classes);
+  while (live) {
+    // the live entries first, a pivot's rows consecutive
+    if ((rc = sd_cas_sort_pairs_dev(c, L.ekey_in, L.erow_in, listed, L.ekey, L.erow, 0, key_bits, s))) return rc;
+    if (c->compare_max_rounds && c->compare_rounds >= c->compare_max_rounds) break;
+    uint32_t after[3] = {0, 0, 0};  // CT_UNEQUAL (of the call so far), CT_UNRESOLVED, CT_OVERFLOW
+    HIP_TRY(c, ct_round(arena, d_offs, d_lens, n, live, L, d_rep_exact, grid, s));
+    HIP_TRY(c, hipMemcpyAsync(after, L.counters + CT_UNEQUAL, 12, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    // 2^32 tasks or more in one round (overlapping contents): nothing ran, the sorted list stands
+    // and the digest route takes it
+    if (after[2]) break;
+    c->compare_rounds++;
+    c->compare_compares += live;
+    c->compare_unequal = after[0];
+    listed = live;
+    live = after[1];
+  }
+  if (live) {
+    c->compare_digest_rows = live;
+    if ((rc = compare_finish_by_digest(c, arena, arena_bytes, d_offs, d_lens, n, live, L, d_rep_exact, s)))
+      return rc;
+  }
+  uint64_t objects = 0;
+  HIP_TRY(c, ct_count_heads(d_rep, d_lens, d_rep_exact, n, c->d_scalar, s));
+  HIP_TRY(c, hipMemcpyAsync(&objects, c->d_scalar, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, sd_ws_release(c, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  c->region_obj_set = -1;
   if (out_objects) *out_objects = objects;
   return SD_CAS_OK;
 }
