@@ -3,7 +3,7 @@
 //   rep_exact[i] = min{ j : class[j] == class[i] && content j == content i },
 //   class[i] = (rep[i] as a value, lens[i])
 // for ragged contents of an arena (content i = arena + offs[i], lens[i] bytes, the layout of
-// sd_cas_checksums_dev).  K1V's compare (cas_hash.hip) at whole-file scale: no digest is taken;
+// sd_cas_checksums_dev).  K1V's compare (dup_verify.hip) at whole-file scale: no digest is taken;
 // the members of a class are compared with each other.
 //
 // Rounds.  Every unresolved row has a pivot, at first its class's first row.  A round compares

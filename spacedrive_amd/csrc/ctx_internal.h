@@ -153,6 +153,31 @@ constexpr uint32_t DUPV_SKIP_CALLS = 16, DUPV_MIN_CANDIDATE_SHARE = 32;
 // SD_CAS_DUP_PLACEMENT: how the workgroups of the verified chain's main kernel get their work
 enum DupPlacement { DUP_PLACE_STATIC = 0, DUP_PLACE_CU = 1, DUP_PLACE_AUTO = 2 };
 
+// The fused chain's duplicate verification (K1V, dup_verify.hip) as the context keeps it.
+struct DupVerifyState {
+  // (sd_cas_set_dup_verify): probes, candidates, lists, flags and counters of the LAST
+  // hash_regions call; a call on another stream waits for that call's region_hashed event before
+  // it refills them
+  DevBuf buf;
+  bool on = true;
+  // SD_CAS_DUP_PLACEMENT=static|cu|auto, read at creation.  static: the tile map fixed before
+  // launch (dup_tile_of); cu: roles taken at run time, at most DUP_CU_LIMIT compare workgroups per
+  // CU (sd_dup_runs.h); auto (the default): cu for a grid of at least DUP_ROLES_MIN_ROUNDS times the
+  // workgroups the chip holds at once (dup_roles_pay), static below
+  DupPlacement placement = DUP_PLACE_AUTO;
+  uint64_t n = 0;           // files of the last verified call (0: none, or the setter was off)
+  hipStream_t stream = nullptr;
+  // Probing a batch costs ~0.3 ms at 1.31 M files whatever it finds, and pays from ~1 candidate
+  // in 32 files on.  Each verified call leaves {seq, candidates, files} in pinned host memory
+  // (note, written by its mixed kernel); a later call that finds a new note with fewer
+  // candidates than that runs plain K1G, and so do the next DUPV_SKIP_CALLS - 1 calls, before
+  // one probes again.  Read without a sync: a note not yet written just means "probe".
+  uint32_t* note = nullptr;
+  uint32_t seq = 0;   // verified calls enqueued so far
+  uint32_t seen = 0;  // the last note's seq acted on
+  uint32_t skip = 0;  // calls left to run without probing
+};
+
 struct sd_cas_ctx {
   int device = 0;
   hipStream_t stream = nullptr;  // compute
@@ -168,10 +193,6 @@ struct sd_cas_ctx {
   DevBuf cvbuf;    // file_checksum: one 32-B CV per 64 MiB segment
   DevBuf io;       // device copies of host arrays (sd_cas_identifier_links)
   DevBuf inplace;  // cas_ids from whole contents: classify's lists (ordered across streams like ws)
-  // the fused chain's duplicate verification (sd_cas_set_dup_verify): probes, candidates, lists,
-  // flags and counters of the LAST hash_regions call; a call on another stream waits for that
-  // call's region_hashed event before it refills them
-  DevBuf dupv;
   // the exact duplicate grouping (sd_cas_group_exact_dev): fast keys, word ids and the mismatch
   // counter, beside ws (which the inner grouping calls use); ordered across streams like ws
   DevBuf exact;
@@ -183,23 +204,7 @@ struct sd_cas_ctx {
   DevBuf contents;
   uint32_t compare_max_rounds = SD_CAS_EXACT_COMPARE_ROUNDS_DEFAULT;  // 0: no cap
   uint64_t compare_rounds = 0, compare_compares = 0, compare_unequal = 0, compare_digest_rows = 0;
-  bool dup_verify = true;
-  // SD_CAS_DUP_PLACEMENT=static|cu|auto, read at creation.  static: the tile map fixed before
-  // launch (dup_tile_of); cu: roles taken at run time, at most DUP_CU_LIMIT compare workgroups per
-  // CU (sd_dup_runs.h); auto (the default): cu for a grid of at least DUP_ROLES_MIN_ROUNDS times the
-  // workgroups the chip holds at once (dup_roles_pay), static below
-  DupPlacement dup_placement = DUP_PLACE_AUTO;
-  uint64_t dupv_n = 0;           // files of the last verified call (0: none, or the setter was off)
-  hipStream_t dupv_stream = nullptr;
-  // Probing a batch costs ~0.3 ms at 1.31 M files whatever it finds, and pays from ~1 candidate
-  // in 32 files on.  Each verified call leaves {seq, candidates, files} in pinned host memory
-  // (dupv_note, written by its mixed kernel); a later call that finds a new note with fewer
-  // candidates than that runs plain K1G, and so do the next DUPV_SKIP_CALLS - 1 calls, before
-  // one probes again.  Read without a sync: a note not yet written just means "probe".
-  uint32_t* dupv_note = nullptr;
-  uint32_t dupv_seq = 0;   // verified calls enqueued so far
-  uint32_t dupv_seen = 0;  // the last note's seq acted on
-  uint32_t dupv_skip = 0;  // calls left to run without probing
+  DupVerifyState dupv;  // the fused chain's duplicate verification (K1V)
   void* pinned = nullptr;
   size_t pinned_bytes = 0;
   uint64_t* d_scalar = nullptr;  // 8 x u64 scratch for counters
@@ -359,7 +364,7 @@ inline hipError_t sd_dev_free(void* p) { return hipFree(p); }
 #endif
 inline const char* sd_buf_name(const sd_cas_ctx* c, const DevBuf& b) {
   return &b == &c->ws ? "ws" : &b == &c->staging ? "staging" : &b == &c->small ? "small"
-       : &b == &c->io ? "io" : &b == &c->inplace ? "inplace" : &b == &c->cvbuf ? "cvbuf" : &b == &c->dupv ? "dupv"
+       : &b == &c->io ? "io" : &b == &c->inplace ? "inplace" : &b == &c->cvbuf ? "cvbuf" : &b == &c->dupv.buf ? "dupv"
        : &b == &c->exact ? "exact"
        : &b == &c->contents ? "contents"
        : &b == &c->regions[0] ? "regions[0]" : &b == &c->regions[1] ? "regions[1]" : "multi";

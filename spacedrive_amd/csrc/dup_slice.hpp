@@ -1,5 +1,5 @@
 // dup_slice.hpp — one slice of a content in a wave's registers and its compare, shared by K1V's
-// row compare (cas_hash.hip) and the whole-content compare (content_compare.hip).  Device only.
+// row compare (dup_verify.hip) and the whole-content compare (content_compare.hip).  Device only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // sd_dup_probe.h — the 64-bit probe that nominates duplicate candidates for the fused chain's
-// verify-by-comparison (cas_hash.hip, K1V).  Plain arithmetic, host and device, so a host
+// verify-by-comparison (dup_verify.hip, K1V).  Plain arithmetic, host and device, so a host
 // program checks its bounds under a sanitizer (tests/native/dup_probe_test.cpp).
 //
 // Two sampled files have the same cas key when their sizes and their 57,344 content bytes are

@@ -1,4 +1,4 @@
-// sd_dup_runs.h — the index arithmetic of K1V's compare tasks (cas_hash.hip).  Plain arithmetic,
+// sd_dup_runs.h — the index arithmetic of K1V's compare tasks (dup_verify.hip).  Plain arithmetic,
 // host and device, so a host program checks it (tests/native/dup_runs_test.cpp).
 //
 // List C holds the candidates ordered by their original (cand[f]), so one original's copies are

@@ -47,6 +47,7 @@ using namespace sdcas;
 namespace sdcas {
 uint32_t sd_dbg_violations_group_hash();
 uint32_t sd_dbg_violations_cas_hash();
+uint32_t sd_dbg_violations_dup_verify();
 uint32_t sd_dbg_violations_group();
 uint32_t sd_dbg_violations_checksum();
 uint32_t sd_dbg_violations_links();
@@ -60,7 +61,8 @@ uint32_t sd_dbg_violations_content_compare();
 // ... plus the allocation tails found changed (below)
 #include "ctx_internal.h"
 extern "C" uint64_t sd_cas_debug_violations(void) {
-  return (uint64_t)sd_dbg_violations_group_hash() + sd_dbg_violations_cas_hash() + sd_dbg_violations_group() +
+  return (uint64_t)sd_dbg_violations_group_hash() + sd_dbg_violations_cas_hash() +
+         sd_dbg_violations_dup_verify() + sd_dbg_violations_group() +
          sd_dbg_violations_checksum() + sd_dbg_violations_links() + sd_dbg_violations_inplace() +
          sd_dbg_violations_object_stats() + sd_dbg_violations_exact_dups() +
          sd_dbg_violations_content_compare() + sd_dbg_tail_check_all();
@@ -256,7 +258,7 @@ int sd_cas_ctx_create(int device, sd_cas_ctx** out) {
       hipEventCreateWithFlags(&c->packed_done, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->ws_ev, hipEventDisableTiming) != hipSuccess ||
       sd_dev_malloc((void**)&c->d_scalar, 64, "d_scalar") != hipSuccess ||
-      hipHostMalloc((void**)&c->dupv_note, 64, hipHostMallocDefault) != hipSuccess ||
+      hipHostMalloc((void**)&c->dupv.note, 64, hipHostMallocDefault) != hipSuccess ||
       sd_dev_malloc((void**)&c->gtotals, GROUP_TOTALS_WORDS * 4, "gtotals") != hipSuccess ||
       hipMemset(c->gtotals, 0, GROUP_TOTALS_WORDS * 4) != hipSuccess ||
       sd_dev_malloc((void**)&c->gcursor, 2 * REGION_SET_WORDS * 4, "gcursor") != hipSuccess ||
@@ -271,7 +273,7 @@ int sd_cas_ctx_create(int device, sd_cas_ctx** out) {
     g_ctx_create_err = "stream/event/scratch creation failed on device " + std::to_string(device);
     return SD_CAS_EHIP;
   }
-  memset(c->dupv_note, 0, 64);
+  memset(c->dupv.note, 0, 64);
   c->quantum = (size_t)prop.multiProcessorCount * 4 * 64;
   {
     const char* t = getenv("SD_CAS_TRACE");
@@ -295,7 +297,7 @@ int sd_cas_ctx_create(int device, sd_cas_ctx** out) {
         g_ctx_create_err = std::string("SD_CAS_DUP_PLACEMENT=") + p + ": static, cu or auto";
         return SD_CAS_EINVAL;
       }
-      c->dup_placement = !strcmp(p, "cu") ? DUP_PLACE_CU : !strcmp(p, "static") ? DUP_PLACE_STATIC : DUP_PLACE_AUTO;
+      c->dupv.placement = !strcmp(p, "cu") ? DUP_PLACE_CU : !strcmp(p, "static") ? DUP_PLACE_STATIC : DUP_PLACE_AUTO;
     }
   }
   bind_pool_to_gpu_node(c);
@@ -348,10 +350,10 @@ void sd_cas_ctx_destroy(sd_cas_ctx* c) {
   if (c->cvbuf.p) (void)sd_dev_free(c->cvbuf.p);
   if (c->io.p) (void)sd_dev_free(c->io.p);
   if (c->inplace.p) (void)sd_dev_free(c->inplace.p);
-  if (c->dupv.p) (void)sd_dev_free(c->dupv.p);
+  if (c->dupv.buf.p) (void)sd_dev_free(c->dupv.buf.p);
   if (c->exact.p) (void)sd_dev_free(c->exact.p);
   if (c->contents.p) (void)sd_dev_free(c->contents.p);
-  if (c->dupv_note) (void)hipHostFree(c->dupv_note);
+  if (c->dupv.note) (void)hipHostFree(c->dupv.note);
   if (c->d_scalar) (void)sd_dev_free(c->d_scalar);
   if (c->gtotals) (void)sd_dev_free(c->gtotals);
   if (c->gcursor) (void)sd_dev_free(c->gcursor);
@@ -395,10 +397,10 @@ int sd_cas_set_group_method(sd_cas_ctx* c, int method, uint64_t bucket_target) {
 int sd_cas_set_dup_verify(sd_cas_ctx* c, int on) {
   if (!c) return SD_CAS_EINVAL;
   if (on != 0 && on != 1) return fail(c, SD_CAS_EINVAL, "set_dup_verify: %d (0 or 1)", on);
-  c->dup_verify = on != 0;
+  c->dupv.on = on != 0;
   // the next call probes, whatever earlier batches held
-  c->dupv_skip = 0;
-  c->dupv_seen = ((volatile uint32_t*)c->dupv_note)[0];
+  c->dupv.skip = 0;
+  c->dupv.seen = ((volatile uint32_t*)c->dupv.note)[0];
   return SD_CAS_OK;
 }
 
@@ -574,6 +576,41 @@ static bool fused_eligible(const sd_cas_ctx* c, size_t n) {
          c->group_target == 0;
 }
 
+// The region target of one set for K1G / K1V: the set's rows and spill list, its cursors, and the
+// caller's rep / overflow.
+static RegionOut region_out(const RegionGroupWs& L, uint32_t* cursor, uint64_t cap, uint32_t* d_rep,
+                            uint32_t* d_overflow) {
+  return RegionOut{L.rkeys, L.rfile, cursor, cap, L.spill_keys, L.spill_file, d_rep, d_overflow,
+                   (unsigned long long*)L.objects};
+}
+
+// Does this hash_regions call verify duplicates (K1V) or run plain K1G?  Not with the setter off,
+// nor during a pause; a new note of an earlier call with too few candidates to pay for the probe
+// starts one (DupVerifyState::note).
+static bool dup_verify_this_call(DupVerifyState& v) {
+  if (!v.on) return false;
+  if (v.skip) {
+    v.skip--;
+    return false;
+  }
+  const volatile uint32_t* note = v.note;
+  const uint32_t seq = note[0], cand = note[1], files = note[2];
+  if (seq != v.seen && note[0] == seq) {
+    v.seen = seq;
+    if ((uint64_t)cand * DUPV_MIN_CANDIDATE_SHARE < files) {
+      v.skip = DUPV_SKIP_CALLS - 1;
+      return false;
+    }
+  }
+  return true;
+}
+
+// K1V's placement for n files: roles taken at run time, or the static tile map
+static bool dup_roles_at_run_time(DupPlacement placement, size_t n, uint32_t cus) {
+  return placement == DUP_PLACE_CU ||
+         (placement == DUP_PLACE_AUTO && dup_roles_pay(dup_role_grid(n), 4 * cus));
+}
+
 int sd_cas_hash_regions_sampled_dev(sd_cas_ctx* c, const void* d_content, uint64_t stride,
                                     const uint64_t* d_sizes, size_t n, uint64_t* d_keys,
                                     uint32_t* d_rep, uint32_t* d_overflow, void* stream) {
@@ -609,49 +646,30 @@ int sd_cas_hash_regions_sampled_dev(sd_cas_ctx* c, const void* d_content, uint64
   c->region_n[k] = n;  // sizes the layout (ensure below grows the set if needed)
   int rc = ensure(c, c->regions[k], region_group_workspace_bytes(n));
   if (rc) return rc;
-  const RegionGroupWs L = region_group_layout(c->regions[k].p, c->region_n[k]);
   uint32_t* cur = c->gcursor + REGION_SET_WORDS * k;
+  const RegionOut ro = region_out(region_group_layout(c->regions[k].p, c->region_n[k]), cur,
+                                  region_capacity(n), d_rep, d_overflow);
+  const uint32_t cus = (uint32_t)(c->quantum / 256);
   hipError_t e;
-  bool verify = c->dup_verify;
-  if (verify && c->dupv_skip) {
-    c->dupv_skip--;
-    verify = false;
-  } else if (verify) {  // has an earlier call reported too few candidates to pay for the probe?
-    const volatile uint32_t* note = c->dupv_note;
-    const uint32_t seq = note[0], cand = note[1], files = note[2];
-    if (seq != c->dupv_seen && note[0] == seq) {
-      c->dupv_seen = seq;
-      if ((uint64_t)cand * DUPV_MIN_CANDIDATE_SHARE < files) {
-        c->dupv_skip = DUPV_SKIP_CALLS - 1;
-        verify = false;
-      }
-    }
-  }
-  if (verify) {  // K1V: duplicate contents are compared, not hashed
-    if ((rc = ensure(c, c->dupv, dup_verify_workspace_bytes(n)))) return rc;
+  if (dup_verify_this_call(c->dupv)) {  // K1V: duplicate contents are compared, not hashed
+    DupVerifyState& v = c->dupv;
+    if ((rc = ensure(c, v.buf, dup_verify_workspace_bytes(n)))) return rc;
     if ((rc = ensure(c, c->ws, hash_group_workspace_bytes(n)))) return rc;
     // the last call's lists, on another stream: after its chain (the other set's event)
-    if (c->dupv_n && c->dupv_stream != s && c->region_cur >= 0)
+    if (v.n && v.stream != s && c->region_cur >= 0)
       HIP_TRY(c, hipStreamWaitEvent(s, c->region_hashed[c->region_cur], 0));
-    const DupVerifyWs D = dup_verify_layout(c->dupv.p, n);
-    const uint32_t cus = (uint32_t)(c->quantum / 256);
-    const bool cu_roles = c->dup_placement == DUP_PLACE_CU ||
-                          (c->dup_placement == DUP_PLACE_AUTO && dup_roles_pay(dup_role_grid(n), 4 * cus));
+    const DupVerifyWs D = dup_verify_layout(v.buf.p, n);
     HIP_TRY(c, sd_ws_acquire(c, s));  // the probes' grouping runs in ws / gtotals
     e = dup_candidates((const uint8_t*)d_content, stride, d_sizes, n, D, c->ws.p, c->gtotals, s);
     HIP_TRY(c, sd_ws_release(c, s));
     if (e == hipSuccess)
-      e = hash_sampled_regions_verify((const uint8_t*)d_content, stride, d_sizes, n, d_keys, d_rep,
-                                      L.rkeys, L.rfile, cur, region_capacity(n), L.spill_keys,
-                                      L.spill_file, d_overflow, L.objects, D, c->dupv_note,
-                                      ++c->dupv_seq, s, cus, cu_roles);
-    c->dupv_n = e == hipSuccess ? n : 0;
-    c->dupv_stream = s;
+      e = hash_sampled_regions_verify((const uint8_t*)d_content, stride, d_sizes, n, d_keys, ro, D, v.note,
+                                      ++v.seq, s, cus, dup_roles_at_run_time(v.placement, n, cus));
+    v.n = e == hipSuccess ? n : 0;
+    v.stream = s;
   } else {
-    e = hash_sampled_regions((const uint8_t*)d_content, stride, d_sizes, n, d_keys, d_rep,
-                             L.rkeys, L.rfile, cur, region_capacity(n), L.spill_keys,
-                             L.spill_file, d_overflow, L.objects, s, (uint32_t)(c->quantum / 256));
-    c->dupv_n = 0;
+    e = hash_sampled_regions((const uint8_t*)d_content, stride, d_sizes, n, d_keys, ro, s, cus);
+    c->dupv.n = 0;
   }
   if (e != hipSuccess) {
     (void)hipMemsetAsync(cur, 0, REGION_SET_WORDS * 4, s);  // restore the cursors' invariant
@@ -666,10 +684,10 @@ int sd_cas_hash_regions_sampled_dev(sd_cas_ctx* c, const void* d_content, uint64
 
 // the counters of the context's last hash_regions call (zeros when it did not verify duplicates)
 static int dup_verify_words(sd_cas_ctx* c, uint32_t (&h)[DUP_COUNTERS]) {
-  if (c->dupv_n && c->region_cur >= 0) {  // the last hash_regions call verified duplicates
+  if (c->dupv.n && c->region_cur >= 0) {  // the last hash_regions call verified duplicates
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamWaitEvent(c->stream, c->region_hashed[c->region_cur], 0));
-    HIP_TRY(c, hipMemcpyAsync(h, dup_verify_layout(c->dupv.p, c->dupv_n).counters, sizeof h,
+    HIP_TRY(c, hipMemcpyAsync(h, dup_verify_layout(c->dupv.buf.p, c->dupv.n).counters, sizeof h,
                               hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
@@ -682,9 +700,9 @@ int sd_cas_dup_verify_counters(sd_cas_ctx* c, uint64_t* out_candidates, uint64_t
   uint32_t h[DUP_COUNTERS] = {0};
   const int rc = dup_verify_words(c, h);
   if (rc) return rc;
-  *out_candidates = h[1];
-  *out_verified = h[2];
-  *out_rehashed = h[3];
+  *out_candidates = h[DUP_N_CAND];
+  *out_verified = h[DUP_VERIFIED];
+  *out_rehashed = h[DUP_REHASHED];
   return SD_CAS_OK;
 }
 
@@ -694,9 +712,9 @@ int sd_cas_dup_verify_rows(sd_cas_ctx* c, uint64_t* out_groups, uint64_t* out_ta
   uint32_t h[DUP_COUNTERS] = {0};
   const int rc = dup_verify_words(c, h);
   if (rc) return rc;
-  *out_groups = h[5];
-  *out_tasks = h[6];
-  *out_references = h[7];
+  *out_groups = h[DUP_GROUPS];
+  *out_tasks = h[DUP_TASKS];
+  *out_references = h[DUP_REFS];
   return SD_CAS_OK;
 }
 

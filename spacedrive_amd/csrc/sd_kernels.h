@@ -28,23 +28,38 @@ namespace sdcas {
 // 256-lane grid (one wave per SIMD instead of half the CUs at two)
 hipError_t hash_sampled(const uint8_t* content, uint64_t stride, const uint64_t* sizes,
                         uint64_t n, uint64_t* keys, hipStream_t s, uint32_t cus);
+// the 512-lane or the 256-lane grid of the sampled kernels for n files (cas_hash.hip)
+bool sampled_grid_is_narrow(uint64_t n, uint32_t cus);
+// Where K1G and K1V put a batch's rows: the fixed-capacity regions of one region set (sd_group.h).
+// A kernel argument: the field order and types are the kernels' ABI.
+struct RegionOut {
+  uint64_t* rkeys;     // [REGIONS][cap] mixed keys
+  uint32_t* rfile;     // [REGIONS][cap] file index
+  uint32_t* cursor;    // [REGION_SET_WORDS] rows reserved per region, then the spill count and
+                       // the full-region count at REGION_SPILL_WORD; zero on entry (the bucket
+                       // tables re-zero them)
+  uint64_t cap;
+  uint64_t* spill_keys;   // rows past their region's capacity (mixed key, file), unordered
+  uint32_t* spill_file;
+  uint32_t* rep;       // rep[f] = f: the bucket tables store only where a key's minimum differs
+  uint32_t* overflow;  // set when a region is full
+  // objects[0]: zeroed here, the bucket tables add the distinct keys; objects[1]: zeroed
+  // here, the tables' carve cursor for the global tables of overflowed regions
+  unsigned long long* objects;
+};
+
 // K1G: K1 + the grouping partition in its epilogue (cas_hash.hip): keys, rep[f] = f, and
-// each key's (mix64(key), f) row in the fixed-capacity region of its coarse bucket
-// (rkeys/rfile [REGIONS][cap], cursor [REGIONS] zero on entry); *overflow |= 1 when a region
-// is full; *objects = 0 (the bucket tables count).
+// each key's (mix64(key), f) row in the region of its coarse bucket; *overflow |= 1 when a
+// region is full; objects[0] = 0 (the bucket tables count).
 hipError_t hash_sampled_regions(const uint8_t* content, uint64_t stride, const uint64_t* sizes,
-                                uint64_t n, uint64_t* keys, uint32_t* rep, uint64_t* rkeys,
-                                uint32_t* rfile, uint32_t* cursor, uint64_t cap, uint64_t* spill_keys,
-                                uint32_t* spill_file, uint32_t* overflow, uint64_t* objects,
-                                hipStream_t s, uint32_t cus);
+                                uint64_t n, uint64_t* keys, const RegionOut& ro, hipStream_t s,
+                                uint32_t cus);
 // K1V: the same outputs as hash_sampled_regions with duplicate contents verified by comparison
-// instead of hashed (cas_hash.hip).  A buffer of the context's own (dup_verify_workspace_bytes(n))
+// instead of hashed (dup_verify.hip).  A buffer of the context's own (dup_verify_workspace_bytes(n))
 // holds the probes, cand (the smallest file with the same probe), the hash and candidate lists,
 // the verified flags, the arrays that order the candidates by original (cnt, first, rank, the
-// scan's partial sums) and counters[DUP_COUNTERS]: files to hash, candidates, verified, rehashed,
-// the task queue, groups, tasks, reference rows read, and the run-time roles' words (the hash-tile
-// queue, compare workgroups started; debug library: hash tiles run and wanted), and cu[DUP_CU_SLOTS],
-// the compare workgroups resident per CU (sd_dup_runs.h), zeroed with the counters.
+// scan's partial sums), counters[DUP_COUNTERS] (the words named below) and cu[DUP_CU_SLOTS], the
+// compare workgroups resident per CU (sd_dup_runs.h), zeroed with the counters.
 // dup_candidates fills probes and cand (the hash grouping: group_ws, totals as hash_group_min);
 // hash_sampled_regions_verify is the rest of the chain and needs neither.  note (pinned host
 // memory, 3 u32, or nullptr): the mixed kernel stores {seq, candidates, n} there, seq last, so
@@ -52,6 +67,14 @@ hipError_t hash_sampled_regions(const uint8_t* content, uint64_t stride, const u
 // kernel's workgroups take their roles at run time (SD_CAS_DUP_PLACEMENT=cu) instead of from the
 // static tile map.
 constexpr uint32_t DUP_COUNTERS = 16;
+// counters: files to hash, candidates, verified, rehashed, the mixed kernel's task queue,
+// groups (originals with a candidate), tasks run, reference rows read (one per run of a task);
+// run-time roles: the hash-tile queue, compare workgroups started; the debug library's conservation
+// check: hash tiles run, and how many the launched grid shape has
+constexpr uint32_t DUP_N_HASH = 0, DUP_N_CAND = 1, DUP_VERIFIED = 2, DUP_REHASHED = 3, DUP_QUEUE = 4,
+                   DUP_GROUPS = 5, DUP_TASKS = 6, DUP_REFS = 7, DUP_HASH_QUEUE = 8, DUP_COMPARE_WGS = 9,
+                   DUP_TILES_RUN = 10, DUP_TILES_WANT = 11;
+static_assert(DUP_TILES_RUN < DUP_TILES_WANT && DUP_TILES_WANT < DUP_COUNTERS, "counters");
 struct DupVerifyWs {
   uint64_t* probes; uint32_t *cand, *list_h, *list_c, *same, *cnt, *first, *rank, *partial, *counters, *cu;
   uint64_t* objects; size_t bytes;
@@ -61,11 +84,9 @@ size_t dup_verify_workspace_bytes(uint64_t n);
 hipError_t dup_candidates(const uint8_t* content, uint64_t stride, const uint64_t* sizes, uint64_t n,
                           const DupVerifyWs& L, void* group_ws, uint32_t* totals, hipStream_t s);
 hipError_t hash_sampled_regions_verify(const uint8_t* content, uint64_t stride, const uint64_t* sizes,
-                                       uint64_t n, uint64_t* keys, uint32_t* rep, uint64_t* rkeys,
-                                       uint32_t* rfile, uint32_t* cursor, uint64_t cap,
-                                       uint64_t* spill_keys, uint32_t* spill_file, uint32_t* overflow,
-                                       uint64_t* objects, const DupVerifyWs& L, uint32_t* note,
-                                       uint32_t seq, hipStream_t s, uint32_t cus, bool cu_roles);
+                                       uint64_t n, uint64_t* keys, const RegionOut& ro,
+                                       const DupVerifyWs& L, uint32_t* note, uint32_t seq,
+                                       hipStream_t s, uint32_t cus, bool cu_roles);
 // pinned host -> device copy by a kernel (16-B aligned; else hipMemcpyAsync)
 hipError_t pull_host(void* dst, const void* src, uint64_t bytes, hipStream_t s);
 hipError_t hash_packed(const uint8_t* arena, const uint64_t* offs, const uint32_t* lens,

@@ -1,6 +1,6 @@
 // sd_mix.h — the grouping's key mix and coarse-bucket function, shared by the grouping
 // kernels (group_hash.hip) and the hash kernels that partition their own output
-// (cas_hash.hip, the fused hash + group chain).
+// (cas_sampled.hpp, the fused hash + group chain).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-"""Planted duplicates for the tests of the fused chain's duplicate verification (cas_hash.hip K1V),
+"""Planted duplicates for the tests of the fused chain's duplicate verification (dup_verify.hip K1V),
 and an independent model of what the chain must make of them (test infrastructure; the logic is
 plain numpy, torch is imported only by the functions that touch the device).
 

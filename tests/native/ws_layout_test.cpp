@@ -16,6 +16,7 @@
 
 #include "ctx_internal.h"
 #include "sd_checksum.h"
+#include "sd_dup_runs.h"
 #include "sd_group.h"
 #include "sd_kernels.h"
 #include "sd_links.h"
@@ -168,6 +169,14 @@ static void layouts() {
       const InplaceWs L = inplace_layout(BASE, n);
       snprintf(key, sizeof key, "inplace(%llu)", un);
       Line(key, L.bytes, inplace_workspace_bytes(n)).M(counters, 8).M(lens32, n * 4).M(sampled_idx, n * 4);
+    }
+    {
+      // K1V: a probe and seven list words per file, exclusive_scan_u32's partial sums per 4,096
+      const DupVerifyWs L = dup_verify_layout(BASE, n);
+      snprintf(key, sizeof key, "dup_verify(%llu)", un);
+      Line(key, L.bytes, dup_verify_workspace_bytes(n)).M(probes, n * 8).M(cand, n * 4).M(list_h, n * 4)
+          .M(list_c, n * 4).M(same, n * 4).M(cnt, n * 4).M(first, n * 4).M(rank, n * 4)
+          .M(partial, (n / 4096 + 1) * 4).M(counters, DUP_COUNTERS * 4).M(cu, DUP_CU_SLOTS * 4).M(objects, 8);
     }
     {
       const PackedWs L = sd_packed_layout(BASE, n);

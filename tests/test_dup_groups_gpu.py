@@ -1,4 +1,4 @@
-"""GPU tests of the fused chain's grouped duplicate verification (cas_hash.hip K1V: candidates
+"""GPU tests of the fused chain's grouped duplicate verification (dup_verify.hip K1V: candidates
 ordered by their original, compare tasks that read an original once per run of its copies).
 Every case checks the keys against the oracle on a sample that holds every edited file, rep and
 the Object count against the standalone grouping, and the exact (candidates, verified, rehashed)

@@ -1,4 +1,4 @@
-"""GPU tests of the two placements of the fused chain's duplicate compares (cas_hash.hip K1V;
+"""GPU tests of the two placements of the fused chain's duplicate compares (dup_verify.hip K1V;
 SD_CAS_DUP_PLACEMENT, read at context creation): `static`, the tile map fixed before launch, and
 `cu`, roles taken at run time by each workgroup (sd_dup_runs.h); `auto`, the default, chooses
 between them by the batch's size.  Every case runs through one context of each placement.  The static context's keys are checked against the oracle on a sample

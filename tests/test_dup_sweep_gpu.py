@@ -1,4 +1,4 @@
-"""GPU tests that sweep the fused chain's duplicate comparison (cas_hash.hip K1V: dup_compare_task,
+"""GPU tests that sweep the fused chain's duplicate comparison (dup_verify.hip K1V: dup_compare_task,
 dup_slices_differ, dup_load_slice, sd_cas_dup_finish_kernel) over every byte of a row and over
 the shapes of its compare tasks.  A wrong "same" verdict merges two files into one Object and
 nothing faults, so every case plants its near misses with tests/dup_plant.py and asserts what

@@ -1,4 +1,4 @@
-"""GPU tests of the fused chain's duplicate verification (cas_hash.hip K1V: probe, candidate
+"""GPU tests of the fused chain's duplicate verification (dup_verify.hip K1V: probe, candidate
 lists, the mixed hash / compare kernel, the finish kernel; sd_cas_set_dup_verify and
 sd_cas_dup_verify_counters).  Every case is one batch quantum, the smallest batch the fused chain
 accepts.  For every case the keys equal the oracle's on a sample of at least 2,048 files that

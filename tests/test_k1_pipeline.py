@@ -1,4 +1,4 @@
-"""K1 / K1G line pipeline (csrc/cas_hash.hip, cas_lane_sampled): every key of a batch against
+"""K1 / K1G line pipeline (csrc/cas_sampled.hpp, cas_lane_sampled): every key of a batch against
 the oracle, at the batch sizes where the dispatch changes the grid.
 
 The lane program walks a file's 448 lines as one sequence and refills each of its two line

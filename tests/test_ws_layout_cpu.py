@@ -78,7 +78,7 @@ def test_every_shape_is_printed(layout_lines):
     ns = [1, 255, 256, 257, 4095, 4096, 4097, 65536, 1441792, 1441793, 12500000, 40000001, 2 ** 32 - 1]
     for n in ns:
         for name in ("sort", "group", "group_min_sorted", "region_group", "small_regions", "big_regions",
-                     "inplace", "packed", "reduce_cvs"):
+                     "inplace", "dup_verify", "packed", "reduce_cvs"):
             assert f"{name}({n})" in layouts
         for t in (0, 1, 16):
             assert f"hash_chain({n},{t})" in layouts

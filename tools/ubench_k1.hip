@@ -10,7 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "../spacedrive_amd/csrc/cas_hash.hip"
+#include "../spacedrive_amd/csrc/cas_sampled.hpp"
 
 // ---- the A/B-only variants of K1's lane program (moved out of the product, round 5) ------
 // NT: non-temporal loads — measured 1.6x SLOWER (33.7 vs 55.0 M files/s): the 8 dwordx4
@@ -41,7 +41,7 @@ __device__ __forceinline__ void load_pair(const uint4* __restrict__ q, uint32_t 
   }
 }
 
-// the product's sdcas::cas_lane_sampled (cas_hash.hip, round 5's loop: both lines loaded at
+// the product's sdcas::cas_lane_sampled (cas_sampled.hpp, round 5's loop: both lines loaded at
 // the iteration start) with the loader swapped — rebased in round 6: the round-5
 // LINE / QUAD / non-temporal rows in profiles/r05/valu_power*/ubench_k1.txt were measured
 // with the older loop that prefetched a pair across the back edge
