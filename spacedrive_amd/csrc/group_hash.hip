@@ -41,6 +41,7 @@
 
 #include "sd_debug.h"
 #include "sd_group.h"
+#include "sd_kernels.h"
 #include "sd_mix.h"
 #include "sd_ws.h"
 
@@ -52,28 +53,12 @@ namespace sdcas {
 constexpr int PART_THREADS = 512;
 constexpr int ITEMS = 8;
 constexpr uint32_t PART_TILE = PART_THREADS * ITEMS;  // 4096 keys per block trip
-#ifndef SD_MIN_THREADS
-#define SD_MIN_THREADS 512
-#endif
-#ifndef SD_MIN_TABLE
-#define SD_MIN_TABLE 4096
-#endif
-constexpr int MIN_THREADS = SD_MIN_THREADS;
+constexpr int MIN_THREADS = 512;
 // keys per thread per trip of the fine-bucket tables (mean bucket <= 1,536 keys: one trip of
-// 2,048) and whether their lookup reuses the insert's slots (A/B: DESIGN.md §2.2)
-#ifndef SD_MIN_ITEMS
-#define SD_MIN_ITEMS 4
-#endif
-#ifndef SD_MIN_KEEP_SLOT
-#define SD_MIN_KEEP_SLOT 1
-#endif
-constexpr int MIN_ITEMS = SD_MIN_ITEMS;
-#ifndef SD_ONE_TRIP_READ_FIRST
-#define SD_ONE_TRIP_READ_FIRST 0
-#endif
-constexpr bool MIN_KEEP_SLOT = SD_MIN_KEEP_SLOT;
-constexpr uint32_t TABLE = SD_MIN_TABLE;  // LDS slots per bucket (4,096: 48 KiB, 3 workgroups/CU)
-constexpr uint32_t BIG_TABLE = 12288;     // sd_bucket_min_big: 144 KiB LDS, 1 workgroup/CU
+// 2,048; 8 keys per lane cost occupancy once the lookup reuses the insert's slots)
+constexpr int MIN_ITEMS = 4;
+constexpr uint32_t TABLE = 4096;       // LDS slots per bucket (4,096: 48 KiB, 3 workgroups/CU)
+constexpr uint32_t BIG_TABLE = 12288;  // sd_bucket_min_big: 144 KiB LDS, 1 workgroup/CU
 constexpr int BIG_THREADS = 1024;
 constexpr uint64_t BIG_MAX_KEYS = 256ull * 5632;  // mean coarse bucket <= 5,632 keys
 constexpr uint32_t MAX_BUCKETS = 16384;   // LDS cursor table of the partition kernels (64 KiB)
@@ -84,25 +69,17 @@ constexpr uint32_t TOTALS_REPL = 16;                  // interleaved copies of t
 // plan the mean bucket may grow to MAX_MEAN_PER_BUCKET distinct keys (LDS table fill 3,584)
 constexpr uint32_t MAX_BITS = 19;
 constexpr uint32_t MAX_B2 = 9;
-#ifndef SD_COARSE10_KEYS
-#define SD_COARSE10_KEYS 40000000
-#endif
-constexpr uint64_t COARSE10_KEYS = SD_COARSE10_KEYS;
+constexpr uint64_t COARSE10_KEYS = 40000000;  // above it the coarse level has 2^10 buckets (group_plan)
 constexpr uint64_t MAX_MEAN_PER_BUCKET = 2500;
 // The fine-bucket tables (one workgroup per ~1,500 keys: 8,192 at 12.5 M keys, 65,536 at
 // 100 M) add their distinct-key counts into OBJ_SHARDS counters, each on a 128-B line of its
 // own (workgroup b into shard b % OBJ_SHARDS), summed into the Object count by one 64-lane
 // launch after them.  Device-scope atomics on ONE counter complete one per ~12.8 ns: 8,192 of
 // them took 105 us where the same workgroups' loads alone took 27 us, and 29 us with 64
-// counters (tools/ubench_bucketload.hip, profiles/r03b_group_ab/).  SD_GROUP_OBJ_SHARDS=1:
-// one counter (the A/B base).
-#ifndef SD_GROUP_OBJ_SHARDS
-#define SD_GROUP_OBJ_SHARDS 64
-#endif
-constexpr uint32_t OBJ_SHARDS = SD_GROUP_OBJ_SHARDS;
-static_assert(OBJ_SHARDS >= 1 && OBJ_SHARDS <= 64, "sd_objects_sum is one wave");
+// counters (tools/ubench_bucketload.hip, profiles/r03b_group_ab/).  64 shards: sd_objects_sum
+// is one wave.
+constexpr uint32_t OBJ_SHARDS = 64;
 constexpr uint32_t OBJ_STRIDE = 16;  // u64 words: one 128-B line per shard
-
 
 // mode 0 (grouping): bucket = top bits of mix64(key), the stored key is mix64(key)
 // mode 1 (range partition): bucket = floor(key * nb / 2^64), the stored key is the key
@@ -200,11 +177,12 @@ __device__ void part_totals_body(const uint64_t* __restrict__ keys, uint64_t n, 
     if (cnt[b]) atomicAdd(&mine[b], cnt[b]);
 }
 
-// Exclusive scan of cnt[0..nb) into out (both LDS) by the whole PART_THREADS block.
+// Exclusive scan of cnt[0..nb) into out (both LDS) by a THREADS-lane block.
+template <int THREADS>
 __device__ void lds_exclusive_scan(const uint32_t* cnt, uint32_t* out, uint32_t nb) {
-  __shared__ uint32_t wsum[PART_THREADS / 64];
+  __shared__ uint32_t wsum[THREADS / 64];
   const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-  const uint32_t per = (nb + PART_THREADS - 1) / PART_THREADS;
+  const uint32_t per = (nb + THREADS - 1) / THREADS;
   const uint32_t lo = t * per < nb ? t * per : nb, hi = lo + per < nb ? lo + per : nb;
   uint32_t sum = 0;
   for (uint32_t i = lo; i < hi; ++i) sum += cnt[i];
@@ -266,7 +244,7 @@ __device__ __forceinline__ void staged_trip(const uint64_t (&k)[ITEMS], const ui
       if (b < nb && tcnt[b]) gcur[b] = bstart[b] + resv[q];
     }
   }
-  lds_exclusive_scan(tcnt, tstart, nb);  // (its barriers also publish gcur)
+  lds_exclusive_scan<PART_THREADS>(tcnt, tstart, nb);  // (its barriers also publish gcur)
   // conservation: the trip's per-bucket counts add up to the trip
   SD_DBG_CHECK(threadIdx.x != 0 || tstart[nb - 1] + tcnt[nb - 1] == trip_n,
                "staged trip (block %u) counted %u of %u keys", blockIdx.x,
@@ -363,7 +341,7 @@ __device__ void part_scatter_body(const uint64_t* __restrict__ keys, uint64_t n,
   }
   __syncthreads();
   if (staged) {
-    lds_exclusive_scan(tcnt, bstart, nb);
+    lds_exclusive_scan<PART_THREADS>(tcnt, bstart, nb);
     for (uint32_t b = threadIdx.x; b < nb; b += PART_THREADS) rbase[b] += bstart[b];
   } else if (threadIdx.x == 0) {  // > 1,024 parts (range mode only, repl = 1): sequential, rare
     uint32_t run = 0;
@@ -675,46 +653,89 @@ __device__ __forceinline__ uint64_t g_find(const uint64_t* tk, uint64_t cap, uin
 // *objects += distinct keys.  gkeys/gvals: 2n-slot overflow tables (touched only on overflow).
 // A bucket of <= TILE keys (all but pathological ones) is loaded once and kept in
 // registers for the lookup; larger buckets stream in TILE trips.
-// KEEP_SLOT: the one-trip lookup reads the slot each key landed in during the insert
-// instead of probing again (round 2 measured it slower for the 4,096-slot tables: with 8
-// keys per lane it cost occupancy; at 4 keys per lane it is the same or faster,
-// profiles/r03b_group_ab/).
-// Regions (the fused hash + group chain): counts != nullptr — bucket b's keys are rows
-// [b * region_cap, b * region_cap + min(counts[b], region_cap)) and the workgroup re-zeroes
-// counts[b] after reading it (the region cursors' persistent-zero invariant).  A region whose
-// count passed its capacity (a key repeated thousands of times) also takes its rows from the
-// spill list (spill_keys/spill_pos[0, *spill_cnt): the rows of every full region, in no
-// order; entries of other regions are skipped) — the same LDS table over region rows +
-// spilled rows, so a hot key costs its own rows, not a pass over the input.  spill_cnt[0]
-// (rows spilled), spill_cnt[1] (full regions, counted by the partition) and spill_cnt[2]
-// (full regions done) are zero on entry; the last full region's workgroup re-zeroes them.  Only when such a region's distinct keys
-// overflow the LDS table too is it regrouped exactly from the whole input rescan[0, rescan_n)
-// (keys of this bucket only) in a global table of 2 x count slots carved from *spill.
-template <uint32_t TBL, int THREADS, int NI, bool KEEP_SLOT>
+// The one-trip lookup reads the slot each key landed in during the insert instead of probing
+// again (round 2 measured that slower for the 4,096-slot tables: with 8 keys per lane it cost
+// occupancy; at 4 keys per lane it is the same or faster, profiles/r03b_group_ab/).
+//
+// BucketRows: where the buckets' rows come from, in one of two shapes.
+// Segments (rows_by_starts): bucket b's rows are pkeys/ppos[starts[b], starts[b + 1]) (n after
+// the last bucket).
+// Regions (rows_by_regions; the fused hash + group chain and the small-batch chain): bucket b's
+// rows are [b * region_cap, b * region_cap + min(counts[b * count_stride], region_cap)) and the
+// workgroup re-zeroes its count after reading it (the region cursors' persistent-zero
+// invariant).  A region whose count passed its capacity (a key repeated thousands of times)
+// also takes its rows from the spill list (SpillList: the rows of every full region, in no
+// order; entries of other regions are skipped) — the same LDS table over region rows + spilled
+// rows, so a hot key costs its own rows, not a pass over the input.  Only when such a region's
+// distinct keys overflow the LDS table too is it regrouped exactly from the whole input
+// (WholeInput; keys of this bucket only) in a global table of 2 x count slots.
+struct SpillList {
+  const uint64_t* keys;  // [0, cnt[0]) mixed keys and their rows
+  const uint32_t* pos;
+  // cnt[0] rows spilled, cnt[1] full regions (counted by the partition), cnt[2] full regions
+  // done: zero on entry; the last full region's workgroup re-zeroes them
+  uint32_t* cnt;
+};
+struct WholeInput {
+  const uint64_t* keys;       // the batch's keys, unmixed
+  uint64_t n;
+  unsigned long long* carve;  // cursor that hands out the global table's slots
+};
+struct BucketRows {
+  const uint64_t* pkeys;
+  const uint32_t* ppos;
+  const uint32_t* vals;  // val(j) = vals ? vals[j] : j
+  uint32_t nb, bits;     // nb = 2^bits buckets
+  const uint32_t* starts;  // segments
+  uint64_t n;
+  uint32_t* counts;        // regions (nullptr: segments)
+  uint32_t count_stride;
+  uint64_t region_cap;
+  SpillList spill;
+  WholeInput rescan;
+  // tests only (the context's SD_CAS_TEST_TABLE_FILL), 0 otherwise: a lower distinct-key bound
+  // for the LDS table, so the overflow and whole-input paths run on keys K1G cannot be made to
+  // produce
+  uint32_t fill_limit;
+};
+__device__ __forceinline__ BucketRows rows_by_starts(const uint64_t* pkeys, const uint32_t* ppos,
+                                                     const uint32_t* vals, const uint32_t* starts,
+                                                     uint32_t nb, uint32_t bits, uint64_t n) {
+  return BucketRows{pkeys, ppos, vals, nb, bits, starts, n, nullptr, 1, 0, SpillList{}, WholeInput{}, 0};
+}
+__device__ __forceinline__ BucketRows rows_by_regions(const uint64_t* rkeys, const uint32_t* rfile,
+                                                      const uint32_t* vals, uint32_t* counts,
+                                                      uint32_t count_stride, uint64_t region_cap,
+                                                      SpillList spill, WholeInput rescan) {
+  return BucketRows{rkeys, rfile, vals, REGIONS, REGION_BITS, nullptr, 0, counts, count_stride,
+                    region_cap, spill, rescan, 0};
+}
+
+template <uint32_t TBL, int THREADS, int NI>
 __device__ __forceinline__ void bucket_min(uint32_t bucket, uint32_t* __restrict__ rezero,
-                                           uint32_t rezero_words,
-                                           const uint64_t* __restrict__ pkeys,
-                                           const uint32_t* __restrict__ ppos,
-                                           const uint32_t* __restrict__ vals,
-                                           const uint32_t* __restrict__ starts, uint32_t nb,
-                                           uint32_t bits, uint64_t n, uint32_t* __restrict__ out,
+                                           uint32_t rezero_words, const BucketRows& rows,
+                                           uint32_t* __restrict__ out,
                                            unsigned long long* __restrict__ objects,
                                            uint64_t* __restrict__ gkeys,
-                                           uint32_t* __restrict__ gvals,
-                                           uint32_t* __restrict__ counts = nullptr,
-                                           uint64_t region_cap = 0,
-                                           const uint64_t* __restrict__ rescan = nullptr,
-                                           uint64_t rescan_n = 0,
-                                           unsigned long long* __restrict__ spill = nullptr,
-                                           uint32_t count_stride = 1,
-                                           const uint64_t* __restrict__ spill_keys = nullptr,
-                                           const uint32_t* __restrict__ spill_pos = nullptr,
-                                           uint32_t* __restrict__ spill_cnt = nullptr,
-                                           uint32_t fill_limit = 0) {
+                                           uint32_t* __restrict__ gvals) {
+  const uint64_t* __restrict__ pkeys = rows.pkeys;
+  const uint32_t* __restrict__ ppos = rows.ppos;
+  const uint32_t* __restrict__ vals = rows.vals;
+  const uint32_t* __restrict__ starts = rows.starts;
+  const uint32_t nb = rows.nb, bits = rows.bits;
+  const uint64_t n = rows.n;
+  uint32_t* __restrict__ counts = rows.counts;
+  const uint32_t count_stride = rows.count_stride;
+  const uint64_t region_cap = rows.region_cap;
+  const uint64_t* __restrict__ spill_keys = rows.spill.keys;
+  const uint32_t* __restrict__ spill_pos = rows.spill.pos;
+  uint32_t* __restrict__ spill_cnt = rows.spill.cnt;
+  const uint64_t* __restrict__ rescan = rows.rescan.keys;
+  const uint64_t rescan_n = rows.rescan.n;
+  unsigned long long* __restrict__ spill = rows.rescan.carve;
+  const uint32_t fill_limit = rows.fill_limit;
   constexpr uint32_t TILE = THREADS * NI;
-  // above FILL distinct keys the bucket goes to global memory; fill_limit (tests only, the
-  // context's SD_CAS_TEST_TABLE_FILL) lowers it so the overflow and whole-input paths run on
-  // keys K1G cannot be made to produce
+  // above FILL distinct keys the bucket goes to global memory (fill_limit lowers it)
   const uint32_t FILL = fill_limit && fill_limit < TBL / 8 * 7 ? fill_limit : TBL / 8 * 7;
   static_assert(TILE < TBL, "one-trip buckets must leave an empty slot (lds_claim's unbounded probe)");
   __shared__ uint64_t tk[TBL];
@@ -731,9 +752,10 @@ __device__ __forceinline__ void bucket_min(uint32_t bucket, uint32_t* __restrict
   // (the persistent buffer's invariant, see hash_group_min)
   if (bucket == 0)
     for (uint32_t i = threadIdx.x; i < rezero_words; i += THREADS) rezero[i] = 0;
-  // rows [s, e_rows) are the bucket's own; [e_rows, e) index the spill list (regions only)
+  const bool regions = counts != nullptr;  // rows in a fixed-capacity region, else a starts[] segment
+  // rows [s, e_rows) are the bucket's own; [e_rows, e) index the spill list (full regions only)
   uint64_t s, e, e_rows;
-  if (counts) {
+  if (regions) {
     if (threadIdx.x == 0) {
       region_n = counts[b * count_stride];
       counts[b * count_stride] = 0;
@@ -755,14 +777,20 @@ __device__ __forceinline__ void bucket_min(uint32_t bucket, uint32_t* __restrict
     __syncthreads();
     s = (uint64_t)b * region_cap;
     e = e_rows = s + (region_n < region_cap ? region_n : region_cap);
-    if (rescan && region_n > region_cap) {
+    if (rescan && region_n > region_cap) {  // (= full, below)
       if (spill_keys) e += sp_n;  // region rows + the spilled rows of this region
-      else e = e_rows = s;        // (uniform) no spill list: straight to the whole-input regroup
+      else e = e_rows = s;        // (= whole) straight to the whole-input regroup
     }
   } else {
     s = starts[b];
     e = e_rows = b + 1 < nb ? starts[b + 1] : n;
   }
+  // (uniform) full: a region past its capacity, exact from its rows + the spill list in LDS, else
+  // from the whole input; whole: no spill list to read, so straight to the whole-input regroup.
+  // (Named after the bounds, which restate the test: set inside the branch above, they change
+  // the region kernels' register allocation.)
+  const bool full = regions && rescan && region_n > region_cap;
+  const bool whole = full && !spill_keys;
   // every stored key of this bucket has top bits == b, so a key from bucket b^1 is never
   // stored; the table is initialised while the bucket bounds are in flight
   const uint64_t empty = (uint64_t)(b ^ 1u) << (64 - bits);
@@ -786,9 +814,6 @@ __device__ __forceinline__ void bucket_min(uint32_t bucket, uint32_t* __restrict
   };
   for (uint32_t i = threadIdx.x; i < TBL; i += THREADS) { tk[i] = empty; tv[i] = 0xFFFFFFFFu; }
   if (threadIdx.x == 0) { distinct = 0; ovf[0] = 0; ovf[1] = 0; }
-  // a region past its capacity: exact from its rows + spill in LDS, else from the whole input
-  const bool full = counts && rescan && region_n > region_cap;
-  const bool whole = full && !spill_keys;
   if (s == e && !whole) return;  // uniform for the whole workgroup
 #if SD_DBG
   __shared__ unsigned int dbg_seen;  // keys inserted: must be the bucket's e - s
@@ -811,7 +836,7 @@ __device__ __forceinline__ void bucket_min(uint32_t bucket, uint32_t* __restrict
 #pragma unroll
       for (int j = 0; j < NI; ++j)
         if (k[j] != empty)
-          sl[j] = lds_claim<TBL, SD_ONE_TRIP_READ_FIRST>(tk, home_slot<TBL>(k[j]), k[j], empty, fresh);
+          sl[j] = lds_claim<TBL>(tk, home_slot<TBL>(k[j]), k[j], empty, fresh);
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
         if (k[j] != empty && sl[j] < TBL) atomicMin(&tv[sl[j]], v[j]);
@@ -856,8 +881,7 @@ __device__ __forceinline__ void bucket_min(uint32_t bucket, uint32_t* __restrict
 #pragma unroll
       for (int j = 0; j < NI; ++j)
         if (k[j] != empty) {
-          const uint32_t mv =
-              tv[KEEP_SLOT ? sl[j] : lds_find<TBL>(tk, home_slot<TBL>(k[j]), k[j])];
+          const uint32_t mv = tv[sl[j]];
           if (mv != v[j]) out[p[j]] = mv;  // out[] was prefilled with the own value
         }
     } else {
@@ -917,10 +941,9 @@ sd_bucket_min(const uint64_t* __restrict__ pkeys, const uint32_t* __restrict__ p
               uint32_t bits, uint64_t n, uint32_t* __restrict__ out,
               unsigned long long* __restrict__ objects, uint64_t* __restrict__ gkeys,
               uint32_t* __restrict__ gvals, uint32_t* __restrict__ rezero, uint32_t rezero_words) {
-  bucket_min<TABLE, MIN_THREADS, MIN_ITEMS, MIN_KEEP_SLOT>(blockIdx.x, rezero, rezero_words, pkeys, ppos,
-                                                          vals, starts, nb, bits, n, out,
-                                                          objects + (blockIdx.x % OBJ_SHARDS) * OBJ_STRIDE,
-                                                          gkeys, gvals);
+  const BucketRows rows = rows_by_starts(pkeys, ppos, vals, starts, nb, bits, n);
+  bucket_min<TABLE, MIN_THREADS, MIN_ITEMS>(blockIdx.x, rezero, rezero_words, rows, out,
+                                            objects + (blockIdx.x % OBJ_SHARDS) * OBJ_STRIDE, gkeys, gvals);
 }
 
 // Small batches (<= BIG_MAX_KEYS): the 2^8 coarse buckets of the first partition level
@@ -935,8 +958,8 @@ sd_bucket_min_big(const uint64_t* __restrict__ pkeys, const uint32_t* __restrict
                   unsigned long long* __restrict__ objects, uint64_t* __restrict__ gkeys,
                   uint32_t* __restrict__ gvals, uint32_t* __restrict__ rezero,
                   uint32_t rezero_words) {
-  bucket_min<BIG_TABLE, BIG_THREADS, ITEMS, true>(blockIdx.x, rezero, rezero_words, pkeys, ppos, vals,
-                                           starts, nb, bits, n, out, objects, gkeys, gvals);
+  const BucketRows rows = rows_by_starts(pkeys, ppos, vals, starts, nb, bits, n);
+  bucket_min<BIG_TABLE, BIG_THREADS, ITEMS>(blockIdx.x, rezero, rezero_words, rows, out, objects, gkeys, gvals);
 }
 
 // The fused chain's bucket tables: one workgroup per region (the coarse buckets K1G wrote),
@@ -959,11 +982,11 @@ sd_bucket_min_regions(const uint64_t* __restrict__ rkeys, const uint32_t* __rest
                       uint32_t* __restrict__ gvals, const uint64_t* __restrict__ keys, uint64_t n,
                       const uint64_t* __restrict__ spill_keys, const uint32_t* __restrict__ spill_file,
                       uint32_t fill_limit) {
-  bucket_min<REG_TABLE, REG_THREADS, REG_ITEMS, true>(blockIdx.x, nullptr, 0, rkeys, rfile, nullptr,
-                                                      nullptr, REGIONS, REGION_BITS, 0, out, objects,
-                                                      gkeys, gvals, cursor, cap, keys, n, objects + 1,
-                                                      1, spill_keys, spill_file,
-                                                      cursor + REGION_SPILL_WORD, fill_limit);
+  BucketRows rows = rows_by_regions(rkeys, rfile, nullptr, cursor, 1, cap,
+                                    SpillList{spill_keys, spill_file, cursor + REGION_SPILL_WORD},
+                                    WholeInput{keys, n, objects + 1});
+  rows.fill_limit = fill_limit;
+  bucket_min<REG_TABLE, REG_THREADS, REG_ITEMS>(blockIdx.x, nullptr, 0, rows, out, objects, gkeys, gvals);
 }
 
 // The standalone chain for small batches (<= BIG_MAX_KEYS keys, default plan): the keys
@@ -976,10 +999,7 @@ sd_bucket_min_regions(const uint64_t* __restrict__ rkeys, const uint32_t* __rest
 // rows.  cursor: REGIONS u32 CURSOR_STRIDE apart (own 128-B lines), then at REGIONS *
 // CURSOR_STRIDE the spill count, the full-region count and the tables' done count; all zero
 // on entry (the tables re-zero them).
-#ifndef SD_REGION_CURSOR_STRIDE
-#define SD_REGION_CURSOR_STRIDE 32
-#endif
-constexpr uint32_t CURSOR_STRIDE = SD_REGION_CURSOR_STRIDE;
+constexpr uint32_t CURSOR_STRIDE = 32;  // u32 words: one 128-B line per cursor
 constexpr int RPART_THREADS = 512;
 constexpr int RPART_ITEMS = 8;
 constexpr uint32_t RPART_TILE = RPART_THREADS * RPART_ITEMS;
@@ -989,7 +1009,6 @@ sd_region_partition(const uint64_t* __restrict__ keys, const uint32_t* __restric
                     uint32_t* __restrict__ cursor, uint64_t cap, uint32_t* __restrict__ out,
                     unsigned long long* __restrict__ objects, unsigned long long* __restrict__ spill,
                     uint64_t* __restrict__ spill_keys, uint32_t* __restrict__ spill_file) {
-  static_assert(RPART_THREADS == PART_THREADS, "lds_exclusive_scan runs on PART_THREADS lanes");
   __shared__ uint32_t tcnt[REGIONS], tstart[REGIONS], gbase[REGIONS], spoff[REGIONS];
   __shared__ uint32_t sp_local, sp_base;
   __shared__ uint64_t skey[RPART_TILE];
@@ -1038,7 +1057,7 @@ sd_region_partition(const uint64_t* __restrict__ keys, const uint32_t* __restric
     spoff[b] = sp ? atomicAdd(&sp_local, sp) : 0u;
     if (g <= cap && g + h > cap) atomicAdd(&cursor[REGIONS * CURSOR_STRIDE + 1], 1u);  // it filled
   }
-  lds_exclusive_scan(tcnt, tstart, REGIONS);  // (its barriers also publish gbase, spoff)
+  lds_exclusive_scan<RPART_THREADS>(tcnt, tstart, REGIONS);  // (its barriers also publish gbase, spoff)
   if (sp_local) {  // (uniform) this tile overflowed a region
     if (threadIdx.x == 0) sp_base = atomicAdd(&cursor[REGIONS * CURSOR_STRIDE], sp_local);
     __syncthreads();
@@ -1085,11 +1104,10 @@ sd_bucket_min_regions_keys(const uint64_t* __restrict__ rkeys, const uint32_t* _
                            uint32_t* __restrict__ gvals, unsigned long long* __restrict__ spill,
                            const uint64_t* __restrict__ spill_keys,
                            const uint32_t* __restrict__ spill_file) {
-  bucket_min<REG_TABLE, REG_THREADS, REG_ITEMS, true>(blockIdx.x, nullptr, 0, rkeys, rfile, vals,
-                                                      nullptr, REGIONS, REGION_BITS, 0, out, objects,
-                                                      gkeys, gvals, cursor, cap, keys, n, spill,
-                                                      CURSOR_STRIDE, spill_keys, spill_file,
-                                                      cursor + REGIONS * CURSOR_STRIDE);
+  const BucketRows rows = rows_by_regions(rkeys, rfile, vals, cursor, CURSOR_STRIDE, cap,
+                                          SpillList{spill_keys, spill_file, cursor + REGIONS * CURSOR_STRIDE},
+                                          WholeInput{keys, n, spill});
+  bucket_min<REG_TABLE, REG_THREADS, REG_ITEMS>(blockIdx.x, nullptr, 0, rows, out, objects, gkeys, gvals);
 }
 
 // The region chain above 1.44 M keys (default plan): one pass of the keys into 2^b1 fixed-
@@ -1099,43 +1117,12 @@ sd_bucket_min_regions_keys(const uint64_t* __restrict__ rkeys, const uint32_t* _
 // capacity go to a spill list (one reservation per workgroup that has any) that the refine of
 // their region reads after its region rows.  The cursors (CURSOR_STRIDE apart) and the spill
 // count live in the persistent totals buffer, zero on entry; the tables re-zero them.
-#ifndef SD_RBIG_THREADS
-#define SD_RBIG_THREADS 1024
-#endif
-#ifndef SD_RBIG_ITEMS
-#define SD_RBIG_ITEMS 8
-#endif
-#ifndef SD_RBIG_MAX_NB
-#define SD_RBIG_MAX_NB 256
-#endif
-constexpr int RBIG_THREADS = SD_RBIG_THREADS;
-constexpr int RBIG_ITEMS = SD_RBIG_ITEMS;
+// (8,192-key tiles: 512 x 8 and 256 x 8 were slower, a resident grid prefetching the next tile
+// and 16,384-key tiles staged in two passes no faster: profiles/r03b_group_ab/README.md "big")
+constexpr int RBIG_THREADS = 1024;
+constexpr int RBIG_ITEMS = 8;
 constexpr uint32_t RBIG_TILE = RBIG_THREADS * RBIG_ITEMS;
-constexpr uint32_t RBIG_MAX_NB = SD_RBIG_MAX_NB;
-
-// Exclusive scan of cnt[0..nb) into out (both LDS) by a THREADS-lane block.
-template <int THREADS>
-__device__ void lds_exclusive_scan_t(const uint32_t* cnt, uint32_t* out, uint32_t nb) {
-  __shared__ uint32_t wsum[THREADS / 64];
-  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-  const uint32_t per = (nb + THREADS - 1) / THREADS;
-  const uint32_t lo = t * per < nb ? t * per : nb, hi = lo + per < nb ? lo + per : nb;
-  uint32_t sum = 0;
-  for (uint32_t i = lo; i < hi; ++i) sum += cnt[i];
-  uint32_t inc = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(inc, o, 64);
-    if (lane >= (uint32_t)o) inc += y;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  uint32_t run = inc - sum;
-  for (uint32_t i = 0; i < w; ++i) run += wsum[i];
-  for (uint32_t i = lo; i < hi; ++i) { out[i] = run; run += cnt[i]; }
-  __syncthreads();
-}
-
+constexpr uint32_t RBIG_MAX_NB = 256;  // coarse regions at most (the LDS arrays below)
 extern "C" __global__ void __launch_bounds__(RBIG_THREADS)
 sd_region_partition_big(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                         uint64_t n, uint32_t rbits, uint64_t* __restrict__ rkeys,
@@ -1184,7 +1171,7 @@ sd_region_partition_big(const uint64_t* __restrict__ keys, const uint32_t* __res
     gbase[b] = g;
     if ((uint64_t)g + h > cap) atomicAdd(&sp_n, (uint32_t)((uint64_t)g + h - (g > cap ? g : cap)));
   }
-  lds_exclusive_scan_t<RBIG_THREADS>(tcnt, tstart, nb);  // (its barriers publish gbase, sp_n)
+  lds_exclusive_scan<RBIG_THREADS>(tcnt, tstart, nb);  // (its barriers publish gbase, sp_n)
   SD_DBG_CHECK(threadIdx.x != 0 || tstart[nb - 1] + tcnt[nb - 1] == tile_n,
                "region partition (block %u) counted %u of %u keys", blockIdx.x,
                tstart[nb - 1] + tcnt[nb - 1], tile_n);
@@ -1274,14 +1261,11 @@ RegionGroupWs region_group_layout(void* ws, uint64_t n) {
 }
 size_t region_group_workspace_bytes(uint64_t n) { return region_group_layout(nullptr, n).bytes; }
 
-hipError_t region_group_min(const uint64_t* rkeys, const uint32_t* rfile, uint32_t* cursor,
-                            uint64_t cap, uint32_t* out, uint64_t* d_objects, uint64_t* gkeys,
-                            uint32_t* gvals, const uint64_t* keys, uint64_t n,
-                            const uint64_t* spill_keys, const uint32_t* spill_file,
+hipError_t region_group_min(const RegionGroupWs& L, const RegionOut& ro, const uint64_t* keys, uint64_t n,
                             uint32_t fill_limit, hipStream_t s) {
-  sd_bucket_min_regions<<<REGIONS, REG_THREADS, 0, s>>>(rkeys, rfile, cursor, cap, out,
-                                                        (unsigned long long*)d_objects, gkeys, gvals,
-                                                        keys, n, spill_keys, spill_file, fill_limit);
+  sd_bucket_min_regions<<<REGIONS, REG_THREADS, 0, s>>>(ro.rkeys, ro.rfile, ro.cursor, ro.cap, ro.rep,
+                                                        ro.objects, L.gkeys, L.gvals, keys, n,
+                                                        ro.spill_keys, ro.spill_file, fill_limit);
   return hipGetLastError();
 }
 
@@ -1342,24 +1326,19 @@ bool hash_group_supported(uint64_t n) {
 
 static uint32_t totals_repl(uint32_t nb) { return nb <= STAGED_MAX_NB ? TOTALS_REPL : 1; }
 
-// The small-batch region chain (sd_region_partition + sd_bucket_min_regions_keys) serves the
-// default plan's batches of (SD_SMALL_REGIONS_MIN, BIG_MAX_KEYS] keys: every one (two launches
-// against totals + scatter + tables: 20 K keys 0.0219 -> 0.0177 ms, 393 K 0.0260 -> 0.0217,
-// 1.31 M 0.0392 -> 0.0314, profiles/r03b_group_ab/README.md "small")
-#ifndef SD_SMALL_REGIONS
-#define SD_SMALL_REGIONS 1
-#endif
-#ifndef SD_SMALL_REGIONS_MIN
-#define SD_SMALL_REGIONS_MIN 0
-#endif
-static bool small_regions(uint64_t n, uint64_t target) {
-  return SD_SMALL_REGIONS && target == 0 && n > SD_SMALL_REGIONS_MIN && n <= BIG_MAX_KEYS;
+// hash_group_min's three chains.  The default plan (target == 0) takes a region chain:
+// SmallRegions (sd_region_partition + sd_bucket_min_regions_keys) for every batch up to
+// BIG_MAX_KEYS keys (two launches against totals + scatter + tables: 20 K keys 0.0219 -> 0.0177
+// ms, 393 K 0.0260 -> 0.0217, 1.31 M 0.0392 -> 0.0314, profiles/r03b_group_ab/README.md "small"),
+// BigRegions for its two-level shapes above that, while the coarse regions fit
+// sd_region_partition_big's LDS.  Everything else — a test's own target, > RBIG_MAX_NB coarse
+// buckets — is TwoLevel: totals + scatter (+ refine) + tables.
+enum class Chain { SmallRegions, BigRegions, TwoLevel };
+static Chain pick_chain(uint64_t n, uint64_t target, const GroupPlan& g) {
+  if (target == 0 && n > 0 && n <= BIG_MAX_KEYS) return Chain::SmallRegions;
+  if (target == 0 && !g.big && g.b2 > 0 && g.l1.nb <= RBIG_MAX_NB) return Chain::BigRegions;
+  return Chain::TwoLevel;
 }
-
-// the region chain above 1.44 M keys: the default plan's two-level shapes
-#ifndef SD_BIG_REGIONS
-#define SD_BIG_REGIONS 1
-#endif
 
 // its workspace: rkeys | rfile | overflow tables (2n slots) | carve cursor | spill list (n rows)
 SmallRegionsWs small_regions_layout(void* ws, uint64_t n) {
@@ -1371,14 +1350,9 @@ SmallRegionsWs small_regions_layout(void* ws, uint64_t n) {
   L.bytes = w.bytes();  return L;
 }
 
-static bool big_regions(const GroupPlan& g, uint64_t target) {
-  return SD_BIG_REGIONS && target == 0 && !g.big && g.b2 > 0 && g.l1.nb <= RBIG_MAX_NB;
-}
-
 // rkeys | rfile | spill keys | spill rows | k2 | p2 | starts | Object-count shards | overflow
-// tables (2n slots).  The default-target plan's layout: big_regions() admits target == 0 only.
-BigRegionsWs big_regions_layout(void* ws, uint64_t n) {
-  const GroupPlan g = group_plan(n, 0);  // (= hash_group_min's plan whenever it takes this chain)
+// tables (2n slots)
+static BigRegionsWs big_regions_carve(void* ws, uint64_t n, const GroupPlan& g) {
   const uint64_t rows = (uint64_t)g.l1.nb * region_capacity_nb(n, g.l1.nb);
   WsCarve w(ws);  BigRegionsWs L;
   L.rkeys = w.take<uint64_t>(rows);  L.rfile = w.take<uint32_t>(rows);
@@ -1388,12 +1362,13 @@ BigRegionsWs big_regions_layout(void* ws, uint64_t n) {
   L.gkeys = w.take<uint64_t>(2 * n);  L.gvals = w.take<uint32_t>(2 * n);
   L.bytes = w.bytes();  return L;
 }
+// the default plan's layout: pick_chain admits target == 0 only
+BigRegionsWs big_regions_layout(void* ws, uint64_t n) { return big_regions_carve(ws, n, group_plan(n, 0)); }
 
 // the two-level chain: k1 | p1 | k2 | p2 | fill (repl copies) | starts1 | starts | Object-count
 // shards | overflow tables (the bucket totals live in a persistent buffer of the caller,
 // GROUP_TOTALS_WORDS)
-HashChainWs hash_chain_layout(void* ws, uint64_t n, uint64_t target) {
-  const GroupPlan g = group_plan(n, target);
+static HashChainWs hash_chain_carve(void* ws, uint64_t n, const GroupPlan& g) {
   const uint64_t nb1 = g.l1.nb;
   WsCarve w(ws);  HashChainWs L;
   L.k1 = w.take<uint64_t>(n);  L.p1 = w.take<uint32_t>(n);
@@ -1403,11 +1378,18 @@ HashChainWs hash_chain_layout(void* ws, uint64_t n, uint64_t target) {
   L.gkeys = w.take<uint64_t>(2 * n);  L.gvals = w.take<uint32_t>(2 * n);
   L.bytes = w.bytes();  return L;
 }
+HashChainWs hash_chain_layout(void* ws, uint64_t n, uint64_t target) {
+  return hash_chain_carve(ws, n, group_plan(n, target));
+}
 // (ws serves whichever chain hash_group_min picks)
 size_t hash_group_workspace_bytes(uint64_t n, uint64_t target) {
-  const size_t chain = hash_chain_layout(nullptr, n, target).bytes;
-  if (small_regions(n, target)) return std::max(chain, small_regions_layout(nullptr, n).bytes);
-  if (big_regions(group_plan(n, target), target)) return std::max(chain, big_regions_layout(nullptr, n).bytes);
+  const GroupPlan g = group_plan(n, target);
+  const size_t chain = hash_chain_carve(nullptr, n, g).bytes;
+  switch (pick_chain(n, target, g)) {
+    case Chain::SmallRegions: return std::max(chain, small_regions_layout(nullptr, n).bytes);
+    case Chain::BigRegions: return std::max(chain, big_regions_carve(nullptr, n, g).bytes);
+    case Chain::TwoLevel: break;
+  }
   return chain;
 }
 
@@ -1450,132 +1432,136 @@ sd_dbg_fill_check(const uint32_t* __restrict__ totals, const uint32_t* __restric
 SD_DBG_ACCESSOR(sd_dbg_violations_group_hash)
 #endif
 
-// totals (zeroed here unless the caller guarantees them zero) -> bucket-contiguous
-// (out_keys, out_pos); starts_out / counts_out
-static hipError_t run_partition(const uint64_t* keys, uint64_t n, const PartPlan& p, int mode,
-                                uint64_t* out_keys, uint32_t* out_pos, uint32_t* totals,
-                                bool totals_zero, uint32_t* fill, uint32_t* starts_out,
-                                uint64_t* counts_out, unsigned long long* objects, uint32_t nobj,
-                                hipStream_t s,
-                                const uint32_t* vals = nullptr, uint32_t* prefill = nullptr) {
-  const uint32_t repl = totals_repl(p.nb);
-  const uint32_t words = repl * p.nb;
-  if (!totals_zero)
-    sd_zero_words<<<(words + 255) / 256 < 64 ? (words + 255) / 256 : 64, 256, 0, s>>>(totals, words);
-  const size_t lds = (size_t)p.nb * 4, slds = scatter_lds_bytes(p.nb);
-  if (mode == 0) {
-    if (vals)
-      sd_part_totals_mix_vals<<<p.nblk, PART_THREADS, lds, s>>>(keys, n, p.nb, p.per_block, totals, repl,
-                                                                fill, objects, nobj, vals, prefill);
-    else
-      sd_part_totals_mix<<<p.nblk, PART_THREADS, lds, s>>>(keys, n, p.nb, p.per_block, totals, repl,
-                                                           fill, objects, nobj, vals, prefill);
-    if (p.nb >= 1024)
-      sd_part_scatter_mix_wide<<<p.nblk, PART_THREADS, slds, s>>>(keys, n, p.nb, p.per_block, totals, repl,
-                                                                  fill, out_keys, out_pos, starts_out);
-    else
-      sd_part_scatter_mix<<<p.nblk, PART_THREADS, slds, s>>>(keys, n, p.nb, p.per_block, totals, repl,
-                                                             fill, out_keys, out_pos, starts_out);
-  } else {
-    sd_part_totals_range<<<p.nblk, PART_THREADS, lds, s>>>(keys, n, p.nb, p.per_block, totals, repl,
-                                                           fill);
-    sd_part_scatter_range<<<p.nblk, PART_THREADS, slds, s>>>(keys, n, p.nb, p.per_block, totals,
-                                                             repl, fill, out_keys, out_pos, counts_out);
-  }
+// after a partition's scatter (debug builds: its conservation check)
+static hipError_t partition_launched(const PartPlan& p, const uint32_t* totals, const uint32_t* fill,
+                                     hipStream_t s) {
 #if SD_DBG
+  const uint32_t words = totals_repl(p.nb) * p.nb;
   sd_dbg_fill_check<<<(words + 255) / 256, 256, 0, s>>>(totals, fill, words);
 #endif
   return hipGetLastError();
 }
 
-// `totals` = the caller's persistent GROUP_TOTALS_WORDS buffer, zero on entry and left zero
-// by the chain's last kernel (the bucket tables zero it once the scatter has read it): the
-// chain needs no zeroing launch of its own (one dependent launch fewer: 1.31M keys ~0.052 ->
-// ~0.048 ms back to back)
+// One hash_group_min call's operands, as its chains take them.  `totals` = the caller's
+// persistent GROUP_TOTALS_WORDS buffer, zero on entry and left zero by the chain's last kernel
+// (the bucket tables zero it once the kernels before them have read it): no chain needs a
+// zeroing launch of its own (one dependent launch fewer: 1.31M keys ~0.052 -> ~0.048 ms back to
+// back).  A chain that fails to launch returns the error; hash_group_min restores the invariant.
+struct GroupCall {
+  const uint64_t* keys;
+  const uint32_t* vals;
+  uint64_t n;
+  uint32_t* out;
+  unsigned long long* objects;
+  uint32_t* totals;
+  hipStream_t s;
+};
+
+// Up to BIG_MAX_KEYS keys: `totals` holds the region cursors, the spill and the done counts.
+static hipError_t small_regions_chain(const GroupCall& c, const SmallRegionsWs& L) {
+  static_assert(REGIONS * CURSOR_STRIDE + 3 <= GROUP_TOTALS_WORDS,
+                "the cursors, spill and done counts fit the totals buffer");
+  const uint64_t cap = region_capacity(c.n);
+  sd_region_partition<<<(uint32_t)((c.n + RPART_TILE - 1) / RPART_TILE), RPART_THREADS, 0, c.s>>>(
+      c.keys, c.vals, c.n, L.rkeys, L.rfile, c.totals, cap, c.out, c.objects, L.spill, L.skeys, L.sfile);
+  sd_bucket_min_regions_keys<<<REGIONS, REG_THREADS, 0, c.s>>>(
+      L.rkeys, L.rfile, c.totals, cap, c.keys, c.vals, c.n, c.out, c.objects, L.gkeys, L.gvals, L.spill,
+      L.skeys, L.sfile);
+  return hipGetLastError();
+}
+
+// The default plan's two-level shapes: `totals` holds the coarse regions' cursors + the spill count.
+static hipError_t big_regions_chain(const GroupCall& c, const GroupPlan& g, const BigRegionsWs& L) {
+  static_assert((1024 + 1) * CURSOR_STRIDE <= GROUP_TOTALS_WORDS,
+                "the big chain's cursors and spill count fit the totals buffer");
+  const uint32_t nb1 = g.l1.nb;
+  const uint64_t cap = region_capacity_nb(c.n, nb1);
+  uint32_t* spill_cnt = c.totals + nb1 * CURSOR_STRIDE;
+  const uint32_t twords = nb1 * CURSOR_STRIDE + CURSOR_STRIDE;
+  const uint64_t tiles = (c.n + RBIG_TILE - 1) / RBIG_TILE;
+  sd_region_partition_big<<<(uint32_t)tiles, RBIG_THREADS, 0, c.s>>>(
+      c.keys, c.vals, c.n, g.b1, L.rkeys, L.rfile, c.totals, cap, c.out, L.shards, OBJ_SHARDS, spill_cnt,
+      L.skeys, L.spos);
+  sd_part_refine_regions<<<nb1, PART_THREADS, 0, c.s>>>(L.rkeys, L.rfile, c.totals, cap, g.b1, g.b2, spill_cnt,
+                                                        L.skeys, L.spos, L.k2, L.p2, L.starts);
+  sd_bucket_min<<<g.nb(), MIN_THREADS, 0, c.s>>>(L.k2, L.p2, c.vals, L.starts, g.nb(), g.b1 + g.b2, c.n, c.out,
+                                                 L.shards, L.gkeys, L.gvals, c.totals, twords);
+  sd_objects_sum<<<1, 64, 0, c.s>>>(L.shards, OBJ_SHARDS, c.objects);
+  return hipGetLastError();
+}
+
+// The coarse level of the two-level chain: totals (zero on entry) -> the keys bucket-contiguous
+// by the top bits of their mix (L.k1, L.p1; L.starts1), out[i] = val(i) prefilled, the nobj
+// Object counters zeroed.
+static hipError_t partition_mix(const GroupCall& c, const PartPlan& p, const HashChainWs& L,
+                                unsigned long long* objects, uint32_t nobj) {
+  const uint32_t repl = totals_repl(p.nb);
+  const size_t lds = (size_t)p.nb * 4, slds = scatter_lds_bytes(p.nb);
+  if (c.vals)
+    sd_part_totals_mix_vals<<<p.nblk, PART_THREADS, lds, c.s>>>(c.keys, c.n, p.nb, p.per_block, c.totals, repl,
+                                                                L.fill, objects, nobj, c.vals, c.out);
+  else
+    sd_part_totals_mix<<<p.nblk, PART_THREADS, lds, c.s>>>(c.keys, c.n, p.nb, p.per_block, c.totals, repl,
+                                                           L.fill, objects, nobj, c.vals, c.out);
+  if (p.nb >= 1024)
+    sd_part_scatter_mix_wide<<<p.nblk, PART_THREADS, slds, c.s>>>(c.keys, c.n, p.nb, p.per_block, c.totals, repl,
+                                                                  L.fill, L.k1, L.p1, L.starts1);
+  else
+    sd_part_scatter_mix<<<p.nblk, PART_THREADS, slds, c.s>>>(c.keys, c.n, p.nb, p.per_block, c.totals, repl,
+                                                             L.fill, L.k1, L.p1, L.starts1);
+  return partition_launched(p, c.totals, L.fill, c.s);
+}
+
+// Every other plan: totals + scatter, the refine where the plan has a second level, the tables.
+static hipError_t two_level_chain(const GroupCall& c, const GroupPlan& g, const HashChainWs& L) {
+  const uint32_t nb1 = g.l1.nb;
+  const uint32_t twords = totals_repl(nb1) * nb1;  // <= GROUP_TOTALS_WORDS
+  // the fine-bucket tables count into the shards (summed after them); the big tables (<= 256
+  // workgroups) straight into the Object count
+  unsigned long long* objects = g.big ? c.objects : L.shards;
+  const hipError_t e = partition_mix(c, g.l1, L, objects, g.big ? 1 : OBJ_SHARDS);
+  if (e != hipSuccess) return e;
+  const uint64_t* fk = L.k1;
+  const uint32_t* fp = L.p1;
+  const uint32_t* fstarts = L.starts1;
+  if (g.b2 > 0) {
+    sd_part_refine<<<nb1, PART_THREADS, 0, c.s>>>(L.k1, L.p1, L.starts1, nb1, c.n, g.b1, g.b2, L.k2, L.p2,
+                                                  L.starts);
+    fk = L.k2;
+    fp = L.p2;
+    fstarts = L.starts;
+  }
+  // (above 1.44M keys, refining into the big tables instead — 4,096 buckets of ~3,050 at
+  // 12.5M — was 1.13x slower: profiles/r02b_group_big_tables_ab.log)
+  if (g.big) {
+    sd_bucket_min_big<<<g.nb(), BIG_THREADS, 0, c.s>>>(fk, fp, c.vals, fstarts, g.nb(), g.b1, c.n, c.out,
+                                                       objects, L.gkeys, L.gvals, c.totals, twords);
+  } else {
+    // one workgroup per fine bucket: a persistent grid walking the buckets (with or without
+    // the next bucket's first trip prefetched) was 2-10 % slower
+    // (profiles/r02b_bucket_min_persist_ab.log); 2,048-slot tables in 256-lane workgroups,
+    // twice the buckets, 1.28x slower (profiles/r02b_group_small_tables_ab.log)
+    sd_bucket_min<<<g.nb(), MIN_THREADS, 0, c.s>>>(fk, fp, c.vals, fstarts, g.nb(), g.b1 + g.b2, c.n, c.out,
+                                                   objects, L.gkeys, L.gvals, c.totals, twords);
+    sd_objects_sum<<<1, 64, 0, c.s>>>(L.shards, OBJ_SHARDS, c.objects);
+  }
+  return hipGetLastError();
+}
+
 hipError_t hash_group_min(const uint64_t* keys, const uint32_t* vals, uint64_t n, uint32_t* out,
                           uint64_t* d_objects, void* ws, uint32_t* totals, hipStream_t s,
                           uint64_t target) {
   if (n == 0) return hipMemsetAsync(d_objects, 0, 8, s);
   if (!hash_group_supported(n)) return hipErrorInvalidValue;
-  static_assert(REGIONS * CURSOR_STRIDE + 3 <= GROUP_TOTALS_WORDS,
-                "the cursors, spill and done counts fit the totals buffer");
-  static_assert((1024 + 1) * CURSOR_STRIDE <= GROUP_TOTALS_WORDS,
-                "the big chain's cursors and spill count fit the totals buffer");
-  if (small_regions(n, target)) {  // `totals` (zero, left zero) holds the region cursors
-    const uint64_t cap = region_capacity(n);
-    const SmallRegionsWs L = small_regions_layout(ws, n);
-    unsigned long long* obj = (unsigned long long*)d_objects;
-    sd_region_partition<<<(uint32_t)((n + RPART_TILE - 1) / RPART_TILE), RPART_THREADS, 0, s>>>(
-        keys, vals, n, L.rkeys, L.rfile, totals, cap, out, obj, L.spill, L.skeys, L.sfile);
-    sd_bucket_min_regions_keys<<<REGIONS, REG_THREADS, 0, s>>>(
-        L.rkeys, L.rfile, totals, cap, keys, vals, n, out, obj, L.gkeys, L.gvals, L.spill, L.skeys, L.sfile);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) (void)hipMemsetAsync(totals, 0, GROUP_TOTALS_WORDS * 4, s);  // restore
-    return e;
-  }
   const GroupPlan g = group_plan(n, target);
-  const size_t nb1 = g.l1.nb;
-  if (big_regions(g, target)) {  // `totals` (zero, left zero) holds the cursors + spill count
-    const uint64_t cap = region_capacity_nb(n, (uint32_t)nb1);
-    const BigRegionsWs L = big_regions_layout(ws, n);
-    uint32_t* spill_cnt = totals + nb1 * CURSOR_STRIDE;
-    const uint32_t twords = (uint32_t)(nb1 * CURSOR_STRIDE + CURSOR_STRIDE);
-    const uint64_t tiles = (n + RBIG_TILE - 1) / RBIG_TILE;
-    // (8,192-key tiles: 512 x 8 and 256 x 8 were slower, a resident grid prefetching the next
-    // tile and 16,384-key tiles staged in two passes no faster: profiles/r03b_group_ab/README.md
-    // "big"; the two-pass variant was removed in round 4)
-    sd_region_partition_big<<<(uint32_t)tiles, RBIG_THREADS, 0, s>>>(
-        keys, vals, n, g.b1, L.rkeys, L.rfile, totals, cap, out, L.shards, OBJ_SHARDS, spill_cnt, L.skeys, L.spos);
-    sd_part_refine_regions<<<(uint32_t)nb1, PART_THREADS, 0, s>>>(
-        L.rkeys, L.rfile, totals, cap, g.b1, g.b2, spill_cnt, L.skeys, L.spos, L.k2, L.p2, L.starts);
-    sd_bucket_min<<<g.nb(), MIN_THREADS, 0, s>>>(L.k2, L.p2, vals, L.starts, g.nb(), g.b1 + g.b2, n, out,
-                                                 L.shards, L.gkeys, L.gvals, totals, twords);
-    sd_objects_sum<<<1, 64, 0, s>>>(L.shards, OBJ_SHARDS, (unsigned long long*)d_objects);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) (void)hipMemsetAsync(totals, 0, GROUP_TOTALS_WORDS * 4, s);  // restore
-    return e;
+  const GroupCall c{keys, vals, n, out, (unsigned long long*)d_objects, totals, s};
+  hipError_t e = hipSuccess;
+  switch (pick_chain(n, target, g)) {
+    case Chain::SmallRegions: e = small_regions_chain(c, small_regions_layout(ws, n)); break;
+    case Chain::BigRegions: e = big_regions_chain(c, g, big_regions_carve(ws, n, g)); break;
+    case Chain::TwoLevel: e = two_level_chain(c, g, hash_chain_carve(ws, n, g)); break;
   }
-  const HashChainWs L = hash_chain_layout(ws, n, target);
-  const uint32_t twords = totals_repl((uint32_t)nb1) * (uint32_t)nb1;  // <= GROUP_TOTALS_WORDS
-  // the fine-bucket tables count into the shards (summed after them); the big tables (<= 256
-  // workgroups) straight into d_objects
-  const bool sharded = !g.big && OBJ_SHARDS > 1;
-  unsigned long long* objects = sharded ? L.shards : (unsigned long long*)d_objects;
-  hipError_t e = run_partition(keys, n, g.l1, 0, L.k1, L.p1, totals, true, L.fill, L.starts1, nullptr,
-                               objects, sharded ? OBJ_SHARDS : 1, s, vals, out);
-  if (e != hipSuccess) {
-    (void)hipMemsetAsync(totals, 0, GROUP_TOTALS_WORDS * 4, s);  // restore the invariant
-    return e;
-  }
-  const uint64_t* fk = L.k1;
-  const uint32_t* fp = L.p1;
-  const uint32_t* fstarts = L.starts1;
-  if (g.b2 > 0) {
-    sd_part_refine<<<(uint32_t)nb1, PART_THREADS, 0, s>>>(L.k1, L.p1, L.starts1, (uint32_t)nb1, n, g.b1,
-                                                          g.b2, L.k2, L.p2, L.starts);
-    fk = L.k2;
-    fp = L.p2;
-    fstarts = L.starts;
-  }
-  // (above 1.44M keys, refining into these big tables instead — 4,096 buckets of ~3,050 at
-  // 12.5M — was 1.13x slower: profiles/r02b_group_big_tables_ab.log)
-  if (g.big)
-    sd_bucket_min_big<<<g.nb(), BIG_THREADS, 0, s>>>(fk, fp, vals, fstarts, g.nb(), g.b1, n, out,
-                                                     (unsigned long long*)d_objects, L.gkeys, L.gvals,
-                                                     totals, twords);
-  else
-    // one workgroup per fine bucket: a persistent grid walking the buckets (with or without
-    // the next bucket's first trip prefetched) was 2-10 % slower
-    // (profiles/r02b_bucket_min_persist_ab.log)
-    // (2,048-slot tables in 256-lane workgroups, twice the buckets: 1.28x slower,
-    // profiles/r02b_group_small_tables_ab.log)
-  {
-    sd_bucket_min<<<g.nb(), MIN_THREADS, 0, s>>>(fk, fp, vals, fstarts, g.nb(), g.b1 + g.b2, n, out,
-                                                 objects, L.gkeys, L.gvals, totals, twords);
-    if (sharded) sd_objects_sum<<<1, 64, 0, s>>>(L.shards, OBJ_SHARDS, (unsigned long long*)d_objects);
-  }
-  e = hipGetLastError();
-  if (e != hipSuccess) (void)hipMemsetAsync(totals, 0, GROUP_TOTALS_WORDS * 4, s);  // restore
+  if (e != hipSuccess) (void)hipMemsetAsync(totals, 0, GROUP_TOTALS_WORDS * 4, s);  // restore the invariant
   return e;
 }
 
@@ -1585,8 +1571,14 @@ hipError_t partition_range(const uint64_t* keys, uint64_t n, uint32_t parts, uin
   if (n == 0) return hipMemsetAsync(d_counts, 0, (size_t)parts * 8, s);
   const PartPlan p = part_plan(n, parts);
   const PartitionWs L = partition_layout(ws, parts);
-  return run_partition(keys, n, p, 1, out_keys, out_pos, L.totals, false, L.fill, nullptr, d_counts,
-                       nullptr, 0, s);
+  const uint32_t repl = totals_repl(p.nb);
+  const uint32_t words = repl * p.nb;  // its totals are its own: zeroed here
+  sd_zero_words<<<(words + 255) / 256 < 64 ? (words + 255) / 256 : 64, 256, 0, s>>>(L.totals, words);
+  sd_part_totals_range<<<p.nblk, PART_THREADS, (size_t)p.nb * 4, s>>>(keys, n, p.nb, p.per_block, L.totals,
+                                                                      repl, L.fill);
+  sd_part_scatter_range<<<p.nblk, PART_THREADS, scatter_lds_bytes(p.nb), s>>>(
+      keys, n, p.nb, p.per_block, L.totals, repl, L.fill, out_keys, out_pos, d_counts);
+  return partition_launched(p, L.totals, L.fill, s);
 }
 
 }  // namespace sdcas

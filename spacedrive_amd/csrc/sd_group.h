@@ -1,4 +1,4 @@
-// sd_group.h — host-side launchers for the sort / grouping kernels (group.hip).
+// sd_group.h — host-side launchers for the sort / grouping kernels (group.hip, group_hash.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -92,15 +92,13 @@ struct RegionGroupWs {
 };
 RegionGroupWs region_group_layout(void* ws, uint64_t n);
 size_t region_group_workspace_bytes(uint64_t n);
-// cursor: the set's REGION_SET_WORDS counters (sd_mix.h); d_objects: 2 u64 (count, overflow
-// carve cursor; K1G zeroed both); spill_keys/spill_file: the rows K1G could not store in
-// their region; keys/n: the batch's key array, read only if a full region's distinct keys
-// overflow its LDS table; fill_limit: 0, or (tests) a lower distinct-key bound for the LDS
-// tables so their overflow paths run
-hipError_t region_group_min(const uint64_t* rkeys, const uint32_t* rfile, uint32_t* cursor,
-                            uint64_t cap, uint32_t* out, uint64_t* d_objects, uint64_t* gkeys,
-                            uint32_t* gvals, const uint64_t* keys, uint64_t n,
-                            const uint64_t* spill_keys, const uint32_t* spill_file,
+// L: the set's buffer (its overflow tables); ro: the region target K1G filled (sd_kernels.h: the
+// rows and spill list, the set's cursors, rep, the Object count and carve cursor K1G zeroed;
+// ro.overflow is not used); keys/n: the batch's key array, read only if a full region's
+// distinct keys overflow its LDS table; fill_limit: 0, or (tests) a lower distinct-key bound
+// for the LDS tables so their overflow paths run
+struct RegionOut;
+hipError_t region_group_min(const RegionGroupWs& L, const RegionOut& ro, const uint64_t* keys, uint64_t n,
                             uint32_t fill_limit, hipStream_t stream);
 // Key-range partition: part(k) = floor(k * parts / 2^64); out_keys/out_pos hold the keys and
 // their input positions part-contiguous (order inside a part unspecified), d_counts[p] the

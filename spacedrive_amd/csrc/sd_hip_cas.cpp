@@ -576,8 +576,8 @@ static bool fused_eligible(const sd_cas_ctx* c, size_t n) {
          c->group_target == 0;
 }
 
-// The region target of one set for K1G / K1V: the set's rows and spill list, its cursors, and the
-// caller's rep / overflow.
+// The region target of one set for K1G / K1V and the bucket tables after them: the set's rows and
+// spill list, its cursors, and the caller's rep / overflow (the tables take no overflow).
 static RegionOut region_out(const RegionGroupWs& L, uint32_t* cursor, uint64_t cap, uint32_t* d_rep,
                             uint32_t* d_overflow) {
   return RegionOut{L.rkeys, L.rfile, cursor, cap, L.spill_keys, L.spill_file, d_rep, d_overflow,
@@ -729,8 +729,8 @@ int sd_cas_group_regions_dev(sd_cas_ctx* c, size_t n, uint32_t* d_rep, uint64_t*
   const RegionGroupWs L = region_group_layout(c->regions[k].p, c->region_n[k]);
   uint32_t* cur = c->gcursor + REGION_SET_WORDS * k;
   HIP_TRY(c, hipStreamWaitEvent(s, c->region_hashed[k], 0));  // after its K1G, whatever stream
-  hipError_t e = region_group_min(L.rkeys, L.rfile, cur, region_capacity(n), d_rep, L.objects, L.gkeys, L.gvals,
-                                  c->region_keys[k], n, L.spill_keys, L.spill_file, c->test_table_fill, s);
+  hipError_t e = region_group_min(L, region_out(L, cur, region_capacity(n), d_rep, nullptr), c->region_keys[k], n,
+                                  c->test_table_fill, s);
   if (e != hipSuccess) {
     (void)hipMemsetAsync(cur, 0, REGION_SET_WORDS * 4, s);
     return fail(c, SD_CAS_EHIP, "group_regions: %s", hipGetErrorString(e));

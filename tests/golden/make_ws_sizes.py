@@ -8,7 +8,8 @@ Two sources, kept apart in the file:
                   and linked against PARENT's libsd_hip_cas.so (functions that commit exports).
                   Run:  python tests/golden/make_ws_sizes.py <that program's output file>
   * "by_formula": totals PARENT computed in static functions or inline, which no program can
-                  call: its formulas, restated below from its source (file:line of PARENT), and
+                  call: its formulas, restated below from its source (file:line of PARENT;
+                  group_hash.hip by the name of the function or constant), and
                   evaluated over the exported inputs (region_capacity, sort_workspace_bytes, ...).
 """
 from __future__ import annotations
@@ -22,10 +23,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 NS = [1, 255, 256, 257, 4095, 4096, 4097, 65536, 1441792, 1441793, 12500000, 40000001, 2 ** 32 - 1]
 TARGETS = [0, 1, 16]
-REGIONS = 256                                      # sd_mix.h:26
-TARGET_PER_BUCKET, MAX_BITS, MAX_B2 = 1536, 19, 9  # group_hash.hip:79,84,85
-BIG_MAX_KEYS, COARSE10_KEYS = 256 * 5632, 40_000_000  # group_hash.hip:77,88
-OBJ_SHARDS, OBJ_STRIDE, TOTALS_REPL, STAGED_MAX_NB = 64, 16, 16, 1024  # group_hash.hip:100,103,81,231
+REGIONS = 256                                      # sd_mix.h
+TARGET_PER_BUCKET, MAX_BITS, MAX_B2 = 1536, 19, 9  # group_hash.hip, constants of the same names
+BIG_MAX_KEYS, COARSE10_KEYS = 256 * 5632, 40_000_000  # (the same)
+OBJ_SHARDS, OBJ_STRIDE, TOTALS_REPL, STAGED_MAX_NB = 64, 16, 16, 1024  # (the same)
 TOP_BINS, TOP_SEL_WORDS = 65, 4                    # sd_object_stats.h:27,28
 
 
@@ -33,7 +34,7 @@ def al(x):
     return (x + 255) // 256 * 256
 
 
-def group_plan(n, target):  # group_hash.hip:1326-1344 -> (l1.nb, nb())
+def group_plan(n, target):  # group_hash.hip group_plan() -> (l1.nb, nb())
     target = target or TARGET_PER_BUCKET
     bits = 1
     while bits < MAX_BITS and (1 << bits) * target < n:
@@ -46,7 +47,7 @@ def group_plan(n, target):  # group_hash.hip:1326-1344 -> (l1.nb, nb())
     return 1 << b1, 1 << (b1 + b2)
 
 
-def region_capacity_nb(n, nb):  # group_hash.hip:1371-1377 (doubles, as there)
+def region_capacity_nb(n, nb):  # group_hash.hip region_capacity_nb() (doubles, as there)
     mean = n / nb
     var = mean * (1.0 - 1.0 / nb)
     sd = 1
@@ -60,15 +61,15 @@ def by_formula(ex):
     sort = lambda n: ex[f"sort_workspace_bytes({n})"]  # noqa: E731
     for n in NS:
         rows = REGIONS * ex[f"region_capacity({n})"]
-        # small_regions_bytes, group_hash.hip:1380-1384
+        # group_hash.hip small_regions_bytes() (since then: small_regions_layout)
         out[f"small_regions({n})"] = (al(rows * 8) + al(rows * 4) + al(2 * n * 8) + al(2 * n * 4) + 256 +
                                       al(n * 8) + al(n * 4))
-        # big_regions_bytes, group_hash.hip:1392-1397
+        # group_hash.hip big_regions_bytes() (since then: big_regions_layout)
         nb1, nb = group_plan(n, 0)
         rows = nb1 * region_capacity_nb(n, nb1)
         out[f"big_regions({n})"] = (al(rows * 8) + al(rows * 4) + 2 * (al(n * 8) + al(n * 4)) + al(nb * 4) +
                                     al(OBJ_SHARDS * OBJ_STRIDE * 8) + al(2 * n * 8) + al(2 * n * 4))
-        for t in TARGETS:  # the `chain` term of hash_group_workspace_bytes, group_hash.hip:1405-1407
+        for t in TARGETS:  # the `chain` term of group_hash.hip hash_group_workspace_bytes()
             nb1, nb = group_plan(n, t)
             repl = TOTALS_REPL if nb1 <= STAGED_MAX_NB else 1
             out[f"hash_chain({n},{t})"] = (2 * (al(n * 8) + al(n * 4)) + al(repl * nb1 * 4) + al(nb1 * 4) +

@@ -527,6 +527,45 @@ def test_group_methods_and_deep_plans(eng, oracle, method, target, n):
         eng.set_group_method()
 
 
+@pytest.mark.parametrize("target,uniform,zero_bits", [
+    (16, 300_000, 15),      # <= 1.44M keys a plan with a refine level goes to the 12,288-slot tables
+                            # instead: 256 buckets, bucket 0 holds ~5,200 distinct keys and fits
+    (1300, 300_000, 15),    # 2^8 buckets and no refine level: sd_bucket_min straight after the scatter
+    (16, 1_450_000, 17),    # > 1.44M keys: b1 = 8, b2 = 9, sd_bucket_min after the refine
+])
+def test_group_min_fine_table_overflow_with_values(eng, oracle, target, uniform, zero_bits):
+    """sd_bucket_min's overflow redo in the global table, with values: uniform keys plus 4,000
+    distinct keys crafted (inverse mix) so their mixed top `zero_bits` bits are 0 — one bucket
+    of the plan, above the 4,096-slot table's 3,584-key fill limit in the second and third case
+    — and 6,000 repeats of them, shuffled.  A non-default bucket target forces the classic
+    chain (totals + scatter [+ refine] + tables).  sd_cas_group_dev vs the oracle and
+    sd_cas_group_min_dev (random u32 vals) vs numpy, Object counts exact."""
+    rng = np.random.default_rng(4000 + target + zero_bits)
+    crafted = np.array([unmix64(int(x) >> zero_bits) for x in rng.integers(0, 2 ** 63, 4000, dtype=np.uint64)],
+                       dtype=np.uint64)
+    keys = np.concatenate([rng.integers(0, 2 ** 64, uniform, dtype=np.uint64), crafted,
+                           crafted[rng.integers(0, len(crafted), 6000)]])
+    keys = keys[rng.permutation(len(keys))]
+    n = len(keys)
+    eng.set_group_method(1, target)
+    try:
+        rep = torch.empty(n, dtype=torch.int32, device="cuda")
+        objects = eng.group(dev64(keys), rep)
+        orep, oobj = oracle.group_canonical(keys)
+        assert objects == oobj
+        assert (rep.cpu().numpy().astype(np.uint32) == orep).all()
+        vals = rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+        out = torch.empty(n, dtype=torch.int32, device="cuda")
+        objects = eng.group_min(dev64(keys), torch.from_numpy(vals.view(np.int32)).cuda(), out)
+        uniq, inv = np.unique(keys, return_inverse=True)
+        mins = np.full(len(uniq), 0xFFFFFFFF, dtype=np.uint32)
+        np.minimum.at(mins, inv, vals)
+        assert objects == len(uniq)
+        assert (out.cpu().numpy().view(np.uint32) == mins[inv]).all()
+    finally:
+        eng.set_group_method()
+
+
 def test_lsd_group_runs_across_tiles(eng, oracle):
     """The LSD grouping's runs kernel (round 6: heads + rep in one pass, a run entering a tile
     found by a galloping lower bound): runs that end exactly at, one before and one after the
