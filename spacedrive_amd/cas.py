@@ -529,7 +529,7 @@ class CasEngine:
         return int(c.value), int(ln.value)
 
     def identifier_links(self, keys, state=None, chunk: int = CHUNK_SIZE,
-                         stream: Optional[int] = None, existing=None, pre_objects=None):
+                         stream: Optional[int] = None, existing=None, pre_objects=None, out=None):
         """Object-link emission of one file-identifier job over the rows (ascending
         file_path.id) — sd_cas_identifier_links_ex_dev: returns (step, object, action)
         device tensors (int32, int32, uint8) and the per-step (created, linked) counts as an
@@ -540,16 +540,23 @@ class CasEngine:
         (action LINK_EXISTING).  pre_objects: None or an int32 device tensor, per row the
         Object its file_path already holds (object_id set, cas_id NULL:
         file_identifier_job.rs:258-261) or -1 (= SD_CAS_NO_OBJECT) — see
-        sd_cas_identifier_links_ex_dev.  Ids must be < 2^31 (checked by the library)."""
+        sd_cas_identifier_links_ex_dev.  Ids must be < 2^31 (checked by the library).
+        out: None or the caller's (step, object, action) tensors to write into."""
         import torch
         n = int(keys.numel())
         _check_dev(keys, (torch.int64, torch.uint64), n, "keys")
         if state is not None:
             _check_dev(state, (torch.uint8,), n, "state")
         dev = keys.device
-        step = torch.empty(n, dtype=torch.int32, device=dev)
-        obj = torch.empty(n, dtype=torch.int32, device=dev)
-        act = torch.empty(n, dtype=torch.uint8, device=dev)
+        if out is not None:
+            step, obj, act = out
+            _check_dev(step, (torch.int32, torch.uint32), n, "out step")
+            _check_dev(obj, (torch.int32, torch.uint32), n, "out object")
+            _check_dev(act, (torch.uint8,), n, "out action")
+        else:
+            step = torch.empty(n, dtype=torch.int32, device=dev)
+            obj = torch.empty(n, dtype=torch.int32, device=dev)
+            act = torch.empty(n, dtype=torch.uint8, device=dev)
         ms = int(self.L.sd_cas_identifier_max_steps(n, int(chunk)))
         counts = np.zeros(2 * max(ms, 1), dtype=np.uint64)
         steps = ctypes.c_uint64(0)
