@@ -450,10 +450,24 @@ def unmix64(m: int) -> int:
 
 
 def test_group_hash_adversarial_keys(eng, oracle):
-    """K4h/K5h on key sets that are not uniform: small integers, one key repeated,
-    8,000 distinct keys crafted (inverse mix) into ONE bucket so its LDS table overflows
-    and the global-memory table takes over, and keys ordered by bucket (maximally unequal
-    per-replica sub-runs in the scatter) — every case vs the oracle's canonical grouping."""
+    """The default plan on key sets that are not uniform, every case vs the oracle's canonical
+    grouping.  Which chain and which exit of bucket_min each case reaches today, by the CPU model
+    of tests/group_cases.py (S = sd_region_partition + the region tables up to 1,441,792 keys,
+    B = sd_region_partition_big + refine + sd_bucket_min above; exits as named there):
+      small ints, iota, bucket-sorted (4 cases): S (B for the 3 M-key pair), every region or
+        bucket one trip, no region full — the keys' order changes the partition's reservations only;
+      one key x100,000: S, one region full (cap 615, 99,385 rows spilled), exact in LDS from its
+        rows + the spill list in 13 trips (spill_lds);
+      zero and max: S, two full regions of one key each, one trip over both regions' spill;
+      crafted overflow / crafted distinct (mixed top 4 bits 0): S, 16 full regions of ~750 rows /
+        ~400 distinct keys (~500 / ~500) against a capacity of 167 (144): spill_lds in two trips
+        (one) — far below the table's fill bound of 10,752, so NOT a table overflow;
+      big-table overflow (1 M keys, 10,000 crafted into region 0): S, region 0 full with 13,732
+        distinct keys: a READ_FIRST claim finds the 12,288-slot table full in trip 2 (claim_fail)
+        and the region is regrouped from the whole input in a carved global table;
+      two-level overflow (1.61 M keys): B, region 0 full (9,274 rows through the spill list into
+        its refine), fine bucket 0 with 10,791 distinct keys redone in its own global table.
+    The exact edges of these paths are in tests/test_group_edges_gpu.py."""
     rng = np.random.default_rng(40)
     crafted = np.array([unmix64(int(x) >> 3) for x in rng.integers(0, 2 ** 63, 8000, dtype=np.uint64)],
                        dtype=np.uint64)  # mix64(key) has top 3 bits 0: all in bucket 0 of 8
