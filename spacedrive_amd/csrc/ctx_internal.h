@@ -1,6 +1,6 @@
 // ctx_internal.h — the sd_cas_ctx object and the host helpers shared by the C-ABI
-// translation units (sd_hip_cas.cpp, host_paths.cpp, validator_host.cpp, sd_multi.cpp).  Not
-// part of the public ABI.
+// translation units (sd_hip_cas.cpp, group_host.cpp, links_host.cpp, reports_host.cpp,
+// host_paths.cpp, validator_host.cpp, sd_multi.cpp).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dirent.h>
@@ -25,6 +25,7 @@
 
 #include "../../include/sd_hip_cas.h"
 #include "sd_debug.h"
+#include "sd_region_sets.h"
 #include "sd_ws.h"
 
 struct DevBuf {
@@ -156,7 +157,7 @@ enum DupPlacement { DUP_PLACE_STATIC = 0, DUP_PLACE_CU = 1, DUP_PLACE_AUTO = 2 }
 // The fused chain's duplicate verification (K1V, dup_verify.hip) as the context keeps it.
 struct DupVerifyState {
   // (sd_cas_set_dup_verify): probes, candidates, lists, flags and counters of the LAST
-  // hash_regions call; a call on another stream waits for that call's region_hashed event before
+  // hash_regions call; a call on another stream waits for that call's `hashed` event before
   // it refills them
   DevBuf buf;
   bool on = true;
@@ -176,6 +177,18 @@ struct DupVerifyState {
   uint32_t seq = 0;   // verified calls enqueued so far
   uint32_t seen = 0;  // the last note's seq acted on
   uint32_t skip = 0;  // calls left to run without probing
+};
+
+// The fused hash + group chain (sd_cas_hash_regions_sampled_dev / sd_cas_group_regions_dev,
+// group_host.cpp): the decisions about its two region sets (sd_region_sets.h) and what performs
+// them.  cursors holds both sets' cursors (2 x REGION_SET_WORDS u32), zero between calls (the
+// tables re-zero); hashed[k] is recorded after set k's K1G (its tables on any stream and its refill
+// wait for it), done[k] after its tables (and after a copy of its Object count).
+struct RegionChain {
+  sdcas::RegionSets sets;
+  uint32_t* cursors = nullptr;
+  DevBuf buf[2];
+  hipEvent_t done[2] = {nullptr, nullptr}, hashed[2] = {nullptr, nullptr};
 };
 
 struct sd_cas_ctx {
@@ -211,26 +224,10 @@ struct sd_cas_ctx {
   // the hash grouping's bucket totals: zero between calls (each call's last kernel re-zeroes
   // them), so the chain has no zeroing launch; ordered across streams like ws
   uint32_t* gtotals = nullptr;
-  // The fused hash + group chain (sd_cas_hash_regions_sampled_dev / sd_cas_group_regions_dev):
-  // two region sets used alternately, so set k's bucket tables can run on a side stream while
-  // the next batch's K1G fills set k^1; region_done[k] orders set k's reuse after its tables.
-  // gcursor holds both sets' cursors (2 x REGIONS u32, <= 1,024), zero between calls (the tables re-zero).
-  uint32_t* gcursor = nullptr;
-  DevBuf regions[2];
-  uint64_t region_n[2] = {0, 0};
-  const uint64_t* region_keys[2] = {nullptr, nullptr};  // the batch's keys (an overflowed region's regroup)
-  hipEvent_t region_done[2] = {nullptr, nullptr};
-  // recorded after set k's K1G: its tables (any stream) and its refill wait for it
-  hipEvent_t region_hashed[2] = {nullptr, nullptr};
-  bool region_pending[2] = {false, false};
-  bool region_grouped[2] = {true, true};  // set k's tables have been enqueued since its K1G
-  int region_cur = -1;
-  // the Object counter of the last grouping call (d_scalar, or a region set's): what
-  // sd_cas_copy_objects_dev copies; region_obj_set = that set (-1: d_scalar)
-  int region_obj_set = -1;
+  RegionChain regions;  // the fused hash + group chain's two region sets
   // ws and d_scalar are shared by every device call of the context, whatever stream the
   // caller passes: the last enqueued use is recorded here and a use on another stream
-  // waits for it first (sd_ws_acquire / sd_ws_release)
+  // waits for it first (WsLease)
   hipEvent_t ws_ev = nullptr;
   hipStream_t ws_stream = nullptr;
   bool ws_pending = false;
@@ -325,9 +322,10 @@ inline int sd_fail(sd_cas_ctx* c, int code, const char* fmt, ...) {
 // default stream (torch's default) must be ordered with our kernels.
 inline hipStream_t sd_pick(sd_cas_ctx*, void* s) { return (hipStream_t)s; }
 
-// Order a use of the shared workspace (ws, d_scalar) on stream s after the previous use
+// Order a use of the shared workspace (ws, d_scalar, gtotals) on stream s after the previous use
 // on any other stream; release records this use.  Calls on one stream need no event wait
-// (stream order), so the single-stream pipelines pay one event record per call.
+// (stream order), so the single-stream pipelines pay one event record per call.  Called by
+// WsLease only.
 inline hipError_t sd_ws_acquire(sd_cas_ctx* c, hipStream_t s) {
   if (c->ws_pending && c->ws_stream != s) return hipStreamWaitEvent(s, c->ws_ev, 0);
   return hipSuccess;
@@ -337,6 +335,32 @@ inline hipError_t sd_ws_release(sd_cas_ctx* c, hipStream_t s) {
   c->ws_pending = true;
   return hipEventRecord(c->ws_ev, s);
 }
+// One use of the shared workspace on a stream, as a scope: constructing it acquires (error()
+// says how that went: a lease whose acquire failed holds nothing), release() records the use once
+// and reports how, and a lease that goes out of scope unreleased (an early return) records it
+// too, so that no path leaves work in ws that the next stream would not wait for.  Leases nest:
+// an outer one around inner public calls that take their own.  Movable, so an object whose
+// begin() acquires can keep it for its caller to release (validator_host.cpp QueueDev).
+class WsLease {
+ public:
+  WsLease() = default;
+  WsLease(sd_cas_ctx* c, hipStream_t s) : s_(s), err_(sd_ws_acquire(c, s)) { c_ = err_ == hipSuccess ? c : nullptr; }
+  WsLease(WsLease&& o) noexcept { *this = std::move(o); }
+  WsLease& operator=(WsLease&& o) noexcept {
+    (void)release();
+    c_ = o.c_;  s_ = o.s_;  err_ = o.err_;  o.c_ = nullptr;
+    return *this;
+  }
+  ~WsLease() { (void)release(); }
+  hipError_t error() const { return err_; }
+  hipError_t release() {
+    sd_cas_ctx* c = c_;  c_ = nullptr;
+    return c ? sd_ws_release(c, s_) : hipSuccess;
+  }
+
+ private:
+  sd_cas_ctx* c_ = nullptr;  hipStream_t s_ = nullptr;  hipError_t err_ = hipSuccess;
+};
 // a 32-byte digest as 64 lower-case hex digits and a NUL
 inline void sd_hex32(const uint8_t d[32], char out[65]) {
   static const char* hx = "0123456789abcdef";
@@ -367,7 +391,7 @@ inline const char* sd_buf_name(const sd_cas_ctx* c, const DevBuf& b) {
        : &b == &c->io ? "io" : &b == &c->inplace ? "inplace" : &b == &c->cvbuf ? "cvbuf" : &b == &c->dupv.buf ? "dupv"
        : &b == &c->exact ? "exact"
        : &b == &c->contents ? "contents"
-       : &b == &c->regions[0] ? "regions[0]" : &b == &c->regions[1] ? "regions[1]" : "multi";
+       : &b == &c->regions.buf[0] ? "regions[0]" : &b == &c->regions.buf[1] ? "regions[1]" : "multi";
 }
 
 // Grow a device buffer (on the CURRENT device).  Growing synchronises the device: call
@@ -414,7 +438,7 @@ extern "C" hipError_t sd_dispatch_packed(sd_cas_ctx* c, const uint8_t* arena, co
                                          uint64_t* keys, hipStream_t s);
 extern "C" size_t sd_packed_workspace_bytes(const sd_cas_ctx* c, size_t n);
 
-// Workspace layouts of sd_hip_cas.cpp, host_paths.cpp (StagedLayout: byte offsets) and sd_multi.cpp
+// Workspace layouts of the C-ABI translation units (host_paths.cpp's StagedLayout: byte offsets)
 // (sd_ws.h; a null base measures).  Internal: exported only so tests/native/ws_layout_test.cpp links them.
 struct PackedWs { uint64_t *lkeys, *skeys; uint32_t* order; void* sort_ws; size_t bytes; };
 struct LinkStagingWs {
@@ -473,3 +497,9 @@ inline int sd_ensure_pinned(sd_cas_ctx* c, size_t bytes) {
   c->pinned_bytes = want;
   return SD_CAS_OK;
 }
+
+// short names for the shared helpers, as the C-ABI translation units write them
+#define fail sd_fail
+#define pick sd_pick
+#define ensure sd_ensure
+#define ensure_pinned sd_ensure_pinned

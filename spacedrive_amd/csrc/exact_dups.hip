@@ -8,7 +8,7 @@
 // Fast path: one u64 key per row from (rep, digest bytes 0..8), the context's grouping over
 // those keys, then a check of every non-head row's full (rep, 32-byte digest) against its
 // head's.  No mismatch = the grouping is exact: equal pairs have equal keys, and every member
-// equals its head.  Any mismatch: the word-wise path (sd_hip_cas.cpp) regroups by one digest
+// equals its head.  Any mismatch: the word-wise path (reports_host.cpp) regroups by one digest
 // word at a time, which is exact by construction.  Elementwise integer passes bound by HBM;
 // digests are read as 16-byte vector loads, every write is a plain vector store or an atomic.
 #include <hip/hip_runtime.h>

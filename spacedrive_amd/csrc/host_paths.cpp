@@ -4,7 +4,7 @@
 // paths: core/src/object/file_identifier/mod.rs:55-95, core/src/object/cas.rs:23-62 — the
 // persistent pread pool at the cas.rs offsets, the streamed single-window pipeline and the
 // windowed double-buffered one), sd_cas_hash_sampled_host[_ring] (config 3's PCIe-inclusive
-// stream).  Split out of sd_hip_cas.cpp; every digest comes from the HIP kernels.
+// stream).  Every digest comes from the HIP kernels.
 #include <errno.h>
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
@@ -32,12 +32,6 @@ using namespace sdcas;
 
 #include "sd_debug.h"
 #include "ctx_internal.h"
-
-// short local names for the shared helpers
-#define fail sd_fail
-#define pick sd_pick
-#define ensure sd_ensure
-#define ensure_pinned sd_ensure_pinned
 
 extern "C" {
 

@@ -1,7 +1,7 @@
 // multi.hip — small kernels of the single-process multi-device grouping (sd_cas_multi_*).
 //
 // The exchange itself is peer copies (hipMemcpyPeerAsync over xGMI) driven by
-// sd_hip_cas.cpp; these kernels compute the key-range split points on the sorted keys,
+// sd_multi.cpp; these kernels compute the key-range split points on the sorted keys,
 // build global file indices, gather run representatives and scatter them back.
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // sd_content_compare.h — launchers of the whole-content compare's kernels (content_compare.hip)
-// and its workspace layout (sd_hip_cas.cpp).
+// and its workspace layout (reports_host.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

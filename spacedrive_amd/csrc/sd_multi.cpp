@@ -20,7 +20,6 @@
 #include <vector>
 
 #include "ctx_internal.h"
-#include "sd_group.h"
 #include "sd_kernels.h"
 #include "sd_multi.h"
 
@@ -409,24 +408,6 @@ int sd_cas_exchange_unpack_fixed_dev(sd_cas_ctx* c, const uint32_t* d_back,
     return sd_fail(c, SD_CAS_EINVAL, "exchange_unpack_fixed: bad arguments");
   HIP_TRY(c, exch_unpack_fixed(d_back, d_spill_back, d_pos, d_counts, G, cap, spill, d_rep,
                                sd_pick(c, stream)));
-  return SD_CAS_OK;
-}
-
-int sd_cas_copy_objects_dev(sd_cas_ctx* c, uint64_t* d_dst, void* stream) {
-  if (!c || !d_dst) return SD_CAS_EINVAL;
-  hipStream_t s = sd_pick(c, stream);
-  const int k = c->region_obj_set;
-  if (k >= 0) {  // the fused chain's last grouping: its region set's counter, after its tables
-    HIP_TRY(c, hipStreamWaitEvent(s, c->region_done[k], 0));
-    const uint64_t* obj = sdcas::region_group_layout(c->regions[k].p, c->region_n[k]).objects;
-    HIP_TRY(c, hipMemcpyAsync(d_dst, obj, 8, hipMemcpyDeviceToDevice, s));
-    // the set's next refill (its K1G zeroes this counter) must also wait for this copy
-    HIP_TRY(c, hipEventRecord(c->region_done[k], s));
-    return SD_CAS_OK;
-  }
-  HIP_TRY(c, sd_ws_acquire(c, s));
-  HIP_TRY(c, hipMemcpyAsync(d_dst, c->d_scalar, 8, hipMemcpyDeviceToDevice, s));
-  HIP_TRY(c, sd_ws_release(c, s));
   return SD_CAS_OK;
 }
 

@@ -2,7 +2,7 @@
 // sd_cas_checksum_dev / sd_cas_file_checksum (file_checksum, core/src/object/validation/
 // hash.rs:9-25: hash.rs's read loop exactly, K3 on the device) and sd_cas_checksums_dev /
 // sd_cas_file_checksums (the validator job over many files, validator_job.rs:107-172: K3b).
-// Split out of sd_hip_cas.cpp; every digest comes from the HIP kernels.
+// Every digest comes from the HIP kernels.
 #include <errno.h>
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
@@ -31,13 +31,6 @@ using namespace sdcas;
 #include "ctx_internal.h"
 #include "sd_piece_queue.h"
 
-// short local names for the shared helpers
-#define fail sd_fail
-#define pick sd_pick
-#define ensure sd_ensure
-#define ensure_pinned sd_ensure_pinned
-
-
 extern "C" {
 
 // ---- file_checksum --------------------------------------------------------------------
@@ -55,7 +48,7 @@ int sd_cas_checksum_dev(sd_cas_ctx* c, const void* d_data, uint64_t len, uint8_t
   int rc = ensure(c, c->ws, batch ? checksum_batch_workspace_bytes(1, len) : checksum_workspace_bytes(len));
   if (rc) return rc;
   uint32_t* d_out = (uint32_t*)c->d_scalar;  // d_scalar[0..3]: digest; [4], [5]: offs, lens
-  HIP_TRY(c, sd_ws_acquire(c, s));
+  WsLease ws(c, s);  HIP_TRY(c, ws.error());
   if (batch) {
     uint64_t* d_ol = c->d_scalar + 4;
     HIP_TRY(c, checksum_single_setup(d_ol, len, (uint32_t*)(c->d_scalar + 6), s));
@@ -65,7 +58,7 @@ int sd_cas_checksum_dev(sd_cas_ctx* c, const void* d_data, uint64_t len, uint8_t
     HIP_TRY(c, checksum_device((const uint8_t*)d_data, len, 0, true, d_out, c->ws.p, s));
   }
   HIP_TRY(c, hipMemcpyAsync(out, d_out, 32, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, sd_ws_release(c, s));
+  HIP_TRY(c, ws.release());
   HIP_TRY(c, hipStreamSynchronize(s));
   return SD_CAS_OK;
 }
@@ -100,14 +93,16 @@ struct SlotEvents {
 
 // The piece queue's device (sd_piece_queue.h): pinned slot -> staging slot over c->copy /
 // c->copy2, the work on c->stream.  begin() runs on the pump thread (HIP's current device is
-// per thread) and takes the workspace; zero: a flag word the unit kernels report into.
+// per thread) and takes the workspace, which the queue's caller releases after the run; zero: a
+// flag word the unit kernels report into.
 struct QueueDev {
   sd_cas_ctx* c;
   uint32_t* zero;
   SlotEvents ev;
+  WsLease ws;
   int begin() {
     hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = sd_ws_acquire(c, c->stream);
+    if (e == hipSuccess) e = (ws = WsLease(c, c->stream)).error();
     if (e == hipSuccess && zero) e = hipMemsetAsync(zero, 0, 4, c->stream);
     return e;
   }
@@ -247,7 +242,7 @@ static int file_checksums_pieces(sd_cas_ctx* c, const char* const* paths, const 
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) rc = fail(c, SD_CAS_EHIP, "checksum digests: %s", hipGetErrorString(e));
   }
-  (void)sd_ws_release(c, s);
+  (void)dev.ws.release();
   for (size_t j = 0; j < nf; j++) {
     errs[j] = ferr[j].load();
     go_seq[j] = !errs[j] && !fok[j];
@@ -319,8 +314,8 @@ static int file_checksum_seq(sd_cas_ctx* c, int fd, const char* path, uint8_t di
     if (err_no) *err_no = (int)-neg;
     return fail(c, SD_CAS_EIO, "read(%s): %s", path, strerror((int)-neg));
   };
-  if (hipError_t e = sd_ws_acquire(c, s); e != hipSuccess)
-    return fail(c, SD_CAS_EHIP, "file_checksum: %s", hipGetErrorString(e));
+  WsLease ws(c, s);
+  if (ws.error() != hipSuccess) return fail(c, SD_CAS_EHIP, "file_checksum: %s", hipGetErrorString(ws.error()));
   uint64_t nseg = 1;
   const int64_t len0 = read_seg(pin[0]);
   if (len0 < 0) {
@@ -352,7 +347,7 @@ static int file_checksum_seq(sd_cas_ctx* c, int fd, const char* path, uint8_t di
     }
   }
   (void)hipStreamSynchronize(s);  // no segment copy may still read the pinned buffers
-  (void)sd_ws_release(c, s);
+  (void)ws.release();
   return rc;
 }
 
@@ -412,12 +407,12 @@ int sd_cas_checksums_dev(sd_cas_ctx* c, const void* d_arena, uint64_t arena_byte
   if (rc) return rc;
   uint32_t* d_bad = (uint32_t*)(c->d_scalar + 6);
   uint32_t bad = 0;
-  HIP_TRY(c, sd_ws_acquire(c, s));
+  WsLease ws(c, s);  HIP_TRY(c, ws.error());
   HIP_TRY(c, hipMemsetAsync(d_bad, 0, 4, s));
   HIP_TRY(c, checksum_batch_device((const uint8_t*)d_arena, arena_bytes, d_offs, d_lens, n,
                                    (uint32_t*)d_out, d_bad, c->ws.p, s));
   HIP_TRY(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, sd_ws_release(c, s));
+  HIP_TRY(c, ws.release());
   HIP_TRY(c, hipStreamSynchronize(s));
   if (bad) return fail(c, SD_CAS_EINVAL, "checksums: %s", batch_bad_message(bad));
   return SD_CAS_OK;
@@ -458,18 +453,15 @@ static int contents_dev(sd_cas_ctx* c, const char* what, const void* d_arena, ui
                                  digests ? checksum_batch_workspace_bytes(n, arena_bytes) : (size_t)0));
   if (rc) return rc;
   uint32_t verdict[2] = {0, 0};  // bad flags, sampled files
-  HIP_TRY(c, sd_ws_acquire(c, s));
+  WsLease ws(c, s);  HIP_TRY(c, ws.error());
   HIP_TRY(c, inplace_classify(arena_bytes, d_offs, d_lens, n, c->inplace.p, s));
   HIP_TRY(c, hipMemcpyAsync(verdict, inplace_layout(c->inplace.p, n).counters, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
-  if (verdict[0]) {
-    (void)sd_ws_release(c, s);
-    return fail(c, SD_CAS_EINVAL, "%s: %s", what, batch_bad_message(verdict[0]));
-  }
+  if (verdict[0]) return fail(c, SD_CAS_EINVAL, "%s: %s", what, batch_bad_message(verdict[0]));
   HIP_TRY(c, contents_hash_classified(c, (const uint8_t*)d_arena, d_offs, d_lens, n, verdict[1],
                                       d_keys, s));
   if (!digests) {
-    HIP_TRY(c, sd_ws_release(c, s));
+    HIP_TRY(c, ws.release());
     return SD_CAS_OK;
   }
   // the chain's own flag can only still report its CV list's bound (overlapping buffers)
@@ -479,7 +471,7 @@ static int contents_dev(sd_cas_ctx* c, const char* what, const void* d_arena, ui
   HIP_TRY(c, checksum_batch_device((const uint8_t*)d_arena, arena_bytes, d_offs, d_lens, n,
                                    (uint32_t*)d_digests, d_bad, c->ws.p, s));
   HIP_TRY(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, sd_ws_release(c, s));
+  HIP_TRY(c, ws.release());
   HIP_TRY(c, hipStreamSynchronize(s));
   if (bad) return fail(c, SD_CAS_EINVAL, "%s: %s", what, batch_bad_message(bad & ~5u));
   return SD_CAS_OK;
@@ -697,7 +689,7 @@ static int file_checksums_impl(sd_cas_ctx* c, const char* const* paths, size_t n
       if (e != hipSuccess) rc = fail(c, SD_CAS_EHIP, "file_checksums: %s", hipGetErrorString(e));
       else if (bad) rc = fail(c, SD_CAS_EHIP, "file_checksums: batch work list overflow");
     }
-    (void)sd_ws_release(c, s);
+    (void)dev.ws.release();
   }
   if (rc) return rc;
   // big regular files: 64 MiB segments of all of them in one piece queue, back to back (after

@@ -81,11 +81,11 @@ def by_formula(ex):
             m = n // 2 + 3
             out[f"multi_bufs({n},{m},{G})"] = (al(n * 8) + al(n * 4) + al(n * 8) + al((G + 1) * 8) + al(n * 8) +
                                                al(m * 8) * 2 + al(m * 8) + al(m * 4) * 2 + al(m * 8) + 256)
-        # top duplicates, sd_hip_cas.cpp:969-970,985-986
+        # top duplicates, sd_cas_top_duplicates_dev (now sd_top_layout, reports_host.cpp)
         small = al(TOP_BINS * 8) + al(TOP_SEL_WORDS * 8) + al(ex[f"top_scan_bytes({n})"])
         out[f"top({n},0)"] = small
         out[f"top({n},{n})"] = small + 2 * (al(n * 8) + al(n * 4)) + sort(n)
-        # the duplicate report, sd_hip_cas.cpp:1041-1044
+        # the duplicate report, sd_cas_duplicate_report (now sd_dup_report_layout, reports_host.cpp)
         b8, b4, b1 = al(n * 8), al(n * 4), al(n)
         for state, k in ((0, 0), (1, 1024)):
             bst = b1 + b8 + 2 * b4 + b8 if state else 0
@@ -93,17 +93,17 @@ def by_formula(ex):
         for pre in (0, 1):
             for n_seed in (0, 5):
                 m, steps = n + n_seed, (n + 99) // 100
-                # the link emission's staging, sd_hip_cas.cpp:679-685
+                # the link emission's staging, sd_cas_identifier_links_ex_dev (now sd_link_staging_layout, links_host.cpp)
                 b = (al(n * 4) + al(m * 8) + al(m * 4) + al(m * 4) + al(n * 8) + al((steps + 1) * 4) +
                      al(steps * 8) + 256)
                 if pre:
                     b += (al(ex[f"pre_blocks({n})"] * 4) + al(ex[f"segmin_tiles_bytes({n})"]) +
                           al(ex["pre_filter_bytes(0)"]))
                 out[f"link_staging({n},{n_seed},{steps},{pre})"] = b
-                # its host arrays' device copies, sd_hip_cas.cpp:841-843
+                # its host arrays' device copies, sd_cas_identifier_links_ex (now sd_link_io_layout, links_host.cpp)
                 out[f"link_io({n},{n_seed},{pre})"] = (al(n * 8) + 2 * al(n) + 2 * al(n * 4) + al(n_seed * 8) +
                                                        al(n_seed * 4) + (al(n * 4) if pre else 0))
-    # object statistics, sd_hip_cas.cpp:917-918
+    # object statistics, object_stats_impl (now sd_stats_layout, reports_host.cpp)
     out["stats()"] = al(ex["stats_shard_bytes(0)"]) + 256
     # the staged host batch, host_paths.cpp:191-195 (plan_batch :70,:73-74 for the two content sizes)
     for ns, np_ in ((0, 1), (1, 0), (100, 0), (37, 63)):
