@@ -435,6 +435,90 @@ int sd_cas_identifier_links_ex(sd_cas_ctx* ctx, const uint64_t* h_keys, const ui
                                uint8_t* h_action, uint64_t* h_step_counts, size_t max_steps,
                                uint64_t* out_steps);
 
+/* ---- Library-resident Object index ---------------------------------------------------------
+ * The library's (cas_id -> Object) relation kept in HBM between calls: what the reference's
+ * SQLite index on cas_id is to every step's find_many by cas_id (file_identifier/mod.rs:181-188),
+ * to the shallow rescan's 100-row steps (file_identifier/shallow.rs:24-118) and to the watcher's
+ * find_first on one cas_id (location/manager/watcher/utils.rs:249-257).  The seeded calls above
+ * take every existing Object as arrays on every call and group n + n_seed keys; an index is
+ * filled as Objects are created and read by later steps, whose cost then depends on their own
+ * rows only.
+ *
+ * An index is a small integer handle of its context (at most SD_CAS_INDEX_MAX alive at once; a
+ * 65th create is SD_CAS_EINVAL, as is every call with a handle that is not alive), destroyed by
+ * sd_cas_index_destroy or with the context.  It maps a u64 cas key — any value, 0 and 2^64-1
+ * included — to the SMALLEST Object id (u32, < 2^31) inserted for it: an open-addressing table
+ * of 16-B slots that grows by itself (expected_entries sizes it up front; 0 = the minimum of
+ * 1,024 slots).
+ *
+ * The contract.  The index caches `min Object id per cas_id` over the library's file_path rows.
+ * It cannot tell which of several ids inserted for a key remain, so when a file_path is deleted
+ * or re-identified the caller ERASES its cas key and RE-INSERTS the (key, id) pairs that remain
+ * for that cas_id — one indexed DB query by cas_id.  That keeps the index exact without a
+ * multimap.  Objects a job creates get their ids from the DB: the caller inserts them after the
+ * job; the link emission only reads the index.
+ *
+ * Ordering.  The library orders the calls on one index itself, whatever streams they are given
+ * (an event per index): a lookup enqueued after an insert sees it.  The caller's own buffers
+ * follow the stream rule at the top of this header.
+ *
+ *   insert  index[key] = min(previous value if any, every id given for key in this call).  An id
+ *           >= 2^31 anywhere in the batch fails the whole call with SD_CAS_EINVAL and inserts
+ *           nothing: the ids are checked on the device first, the _dev form waits for that
+ *           verdict only and then enqueues (as sd_cas_hash_contents_dev does).  A batch that may
+ *           pass the table's load is preceded by a rehash (grow, or the same size when
+ *           tombstones filled it), which blocks.
+ *   lookup  d_objects[i] = the id of d_keys[i], or SD_CAS_NO_OBJECT.  Asynchronous.  The host
+ *           form is the watcher's find_first.
+ *   erase   removes the keys whatever id they hold; an absent key is a no-op, a key repeated in
+ *           the batch is fine.  Asynchronous.
+ *   insert, lookup and erase take n < 2^32 keys per call (SD_CAS_EINVAL from 2^32 on, nothing
+ *           done); n == 0 launches nothing.
+ *   clear   empties the index (its table keeps its size).  Asynchronous.
+ *   export  the live (key, id) pairs in unspecified order, *out_n = their number.  Blocking.
+ *           cap < that number: SD_CAS_EINVAL, nothing written except *out_n.
+ *   stats   out[SD_CAS_INDEX_STAT_*]: ENTRIES (live keys), SLOTS, TOMBSTONES, REHASHES (since
+ *           create / clear), LAST_MAX_PROBE (the most slots one key examined in the last insert,
+ *           lookup or erase; 0 when that call had n == 0), three reserved zeros.  Blocking. */
+#define SD_CAS_INDEX_MAX 64
+#define SD_CAS_INDEX_STAT_ENTRIES 0
+#define SD_CAS_INDEX_STAT_SLOTS 1
+#define SD_CAS_INDEX_STAT_TOMBSTONES 2
+#define SD_CAS_INDEX_STAT_REHASHES 3
+#define SD_CAS_INDEX_STAT_LAST_MAX_PROBE 4
+int sd_cas_index_create(sd_cas_ctx* ctx, uint64_t expected_entries, uint32_t* out_index);
+int sd_cas_index_destroy(sd_cas_ctx* ctx, uint32_t index);
+int sd_cas_index_clear(sd_cas_ctx* ctx, uint32_t index, void* stream);
+int sd_cas_index_insert_dev(sd_cas_ctx* ctx, uint32_t index, const uint64_t* d_keys,
+                            const uint32_t* d_objects, size_t n, void* stream);
+int sd_cas_index_insert(sd_cas_ctx* ctx, uint32_t index, const uint64_t* h_keys,
+                        const uint32_t* h_objects, size_t n);
+int sd_cas_index_lookup_dev(sd_cas_ctx* ctx, uint32_t index, const uint64_t* d_keys, size_t n,
+                            uint32_t* d_objects, void* stream);
+int sd_cas_index_lookup(sd_cas_ctx* ctx, uint32_t index, const uint64_t* h_keys, size_t n,
+                        uint32_t* h_objects);
+int sd_cas_index_erase_dev(sd_cas_ctx* ctx, uint32_t index, const uint64_t* d_keys, size_t n,
+                           void* stream);
+int sd_cas_index_erase(sd_cas_ctx* ctx, uint32_t index, const uint64_t* h_keys, size_t n);
+int sd_cas_index_export_dev(sd_cas_ctx* ctx, uint32_t index, uint64_t* d_keys, uint32_t* d_objects,
+                            size_t cap, uint64_t* out_n, void* stream);
+int sd_cas_index_stats(sd_cas_ctx* ctx, uint32_t index, uint64_t out[8]);
+/* sd_cas_identifier_links_ex[_dev] with the existing Objects read from an index instead of seed
+ * arrays: every output, the per-step counts and the error rules are those of the seeded call
+ * given the index's exported pairs as seeds (an empty index: the fresh-library call).  The rows
+ * alone are grouped and each hashed row looks its key up, so the cost does not depend on the
+ * size of the library.  n < 2^31.  Blocking, like the calls above. */
+int sd_cas_identifier_links_indexed_dev(sd_cas_ctx* ctx, const uint64_t* d_keys, const uint8_t* d_state,
+                                        size_t n, uint32_t chunk, uint32_t index,
+                                        const uint32_t* d_pre_objects, uint32_t* d_step,
+                                        uint32_t* d_object, uint8_t* d_action, uint64_t* h_step_counts,
+                                        size_t max_steps, uint64_t* out_steps, void* stream);
+int sd_cas_identifier_links_indexed(sd_cas_ctx* ctx, const uint64_t* h_keys, const uint8_t* h_state,
+                                    size_t n, uint32_t chunk, uint32_t index,
+                                    const uint32_t* h_pre_objects, uint32_t* h_step, uint32_t* h_object,
+                                    uint8_t* h_action, uint64_t* h_step_counts, size_t max_steps,
+                                    uint64_t* out_steps);
+
 /* ---- Object statistics: copies, unique bytes, top duplicate sets -------------------------
  * What a grouping is worth.  The reference keeps the slot and leaves it empty:
  * core/src/library/statistics.rs:42,46 writes total_object_count = 0 and total_unique_bytes

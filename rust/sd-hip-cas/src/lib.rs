@@ -36,6 +36,12 @@ pub const SD_CAS_LINK_EXISTING: u8 = 4;
 pub const SD_CAS_NO_OBJECT: u32 = 0xFFFF_FFFF;
 pub const SD_CAS_NO_STEP: u32 = 0xFFFF_FFFF;
 pub const SD_CAS_CHUNK_SIZE: u32 = 100;
+pub const SD_CAS_INDEX_MAX: usize = 64;
+pub const SD_CAS_INDEX_STAT_ENTRIES: usize = 0;
+pub const SD_CAS_INDEX_STAT_SLOTS: usize = 1;
+pub const SD_CAS_INDEX_STAT_TOMBSTONES: usize = 2;
+pub const SD_CAS_INDEX_STAT_REHASHES: usize = 3;
+pub const SD_CAS_INDEX_STAT_LAST_MAX_PROBE: usize = 4;
 pub const SD_CAS_STAT_ROWS: usize = 0;
 pub const SD_CAS_STAT_OBJECTS: usize = 1;
 pub const SD_CAS_STAT_TOTAL_BYTES: usize = 2;
@@ -175,6 +181,36 @@ extern "C" {
                                       h_object: *mut u32, h_action: *mut u8,
                                       h_step_counts: *mut u64, max_steps: usize,
                                       out_steps: *mut u64) -> c_int;
+    pub fn sd_cas_index_create(ctx: *mut sd_cas_ctx, expected_entries: u64, out_index: *mut u32) -> c_int;
+    pub fn sd_cas_index_destroy(ctx: *mut sd_cas_ctx, index: u32) -> c_int;
+    pub fn sd_cas_index_clear(ctx: *mut sd_cas_ctx, index: u32, stream: *mut c_void) -> c_int;
+    pub fn sd_cas_index_insert_dev(ctx: *mut sd_cas_ctx, index: u32, d_keys: *const u64,
+                                   d_objects: *const u32, n: usize, stream: *mut c_void) -> c_int;
+    pub fn sd_cas_index_insert(ctx: *mut sd_cas_ctx, index: u32, h_keys: *const u64,
+                               h_objects: *const u32, n: usize) -> c_int;
+    pub fn sd_cas_index_lookup_dev(ctx: *mut sd_cas_ctx, index: u32, d_keys: *const u64, n: usize,
+                                   d_objects: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn sd_cas_index_lookup(ctx: *mut sd_cas_ctx, index: u32, h_keys: *const u64, n: usize,
+                               h_objects: *mut u32) -> c_int;
+    pub fn sd_cas_index_erase_dev(ctx: *mut sd_cas_ctx, index: u32, d_keys: *const u64, n: usize,
+                                  stream: *mut c_void) -> c_int;
+    pub fn sd_cas_index_erase(ctx: *mut sd_cas_ctx, index: u32, h_keys: *const u64, n: usize) -> c_int;
+    pub fn sd_cas_index_export_dev(ctx: *mut sd_cas_ctx, index: u32, d_keys: *mut u64,
+                                   d_objects: *mut u32, cap: usize, out_n: *mut u64,
+                                   stream: *mut c_void) -> c_int;
+    pub fn sd_cas_index_stats(ctx: *mut sd_cas_ctx, index: u32, out: *mut u64) -> c_int;
+    pub fn sd_cas_identifier_links_indexed_dev(ctx: *mut sd_cas_ctx, d_keys: *const u64, d_state: *const u8,
+                                               n: usize, chunk: u32, index: u32,
+                                               d_pre_objects: *const u32, d_step: *mut u32,
+                                               d_object: *mut u32, d_action: *mut u8,
+                                               h_step_counts: *mut u64, max_steps: usize,
+                                               out_steps: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sd_cas_identifier_links_indexed(ctx: *mut sd_cas_ctx, h_keys: *const u64, h_state: *const u8,
+                                           n: usize, chunk: u32, index: u32,
+                                           h_pre_objects: *const u32, h_step: *mut u32,
+                                           h_object: *mut u32, h_action: *mut u8,
+                                           h_step_counts: *mut u64, max_steps: usize,
+                                           out_steps: *mut u64) -> c_int;
     pub fn sd_cas_object_stats_dev(ctx: *mut sd_cas_ctx, d_rep: *const u32, d_sizes: *const u64,
                                    n: usize, d_copies: *mut u32, d_totals: *mut u64,
                                    out_totals: *mut u64, stream: *mut c_void) -> c_int;
@@ -374,6 +410,13 @@ pub struct ExactStatistics {
     pub unconfirmed: u64,
 }
 
+/// A library-resident Object index: a handle of the `HipCas` that made it (`object_index`),
+/// valid until `index_destroy` or the end of that context.  Not Clone: one owner.
+#[derive(Debug, PartialEq, Eq)]
+pub struct ObjectIndex {
+    handle: u32,
+}
+
 /// One context per (job thread, device).  Not Sync; Send is fine.
 pub struct HipCas {
     ctx: *mut sd_cas_ctx,
@@ -512,6 +555,21 @@ impl HipCas {
     /// creates (mod.rs:202-253) — sd_cas_identifier_links_ex.
     pub fn identifier_links_orphans(&mut self, rows: &[OrphanRow], chunk: u32,
                                     existing: &[ExistingObject]) -> io::Result<Vec<StepBatch>> {
+        self.links_with(rows, chunk, existing, None)
+    }
+
+    /// The same job with the library's Objects read from a resident `ObjectIndex` of this
+    /// context instead of an `existing` slice (sd_cas_identifier_links_indexed): the batches are
+    /// those of `identifier_links_orphans` given the index's pairs, at a cost that does not
+    /// depend on the size of the library.  The index is only read: insert the Objects the DB
+    /// created for `creates` afterwards.
+    pub fn identifier_links_indexed(&mut self, rows: &[OrphanRow], chunk: u32,
+                                    index: &ObjectIndex) -> io::Result<Vec<StepBatch>> {
+        self.links_with(rows, chunk, &[], Some(index.handle))
+    }
+
+    fn links_with(&mut self, rows: &[OrphanRow], chunk: u32, existing: &[ExistingObject],
+                  index: Option<u32>) -> io::Result<Vec<StepBatch>> {
         let n = rows.len();
         let keys: Vec<u64> = rows.iter().map(|r| if let RowState::Hashed(k) = r.state { k.0 } else { 0 }).collect();
         let state: Vec<u8> = rows
@@ -532,12 +590,19 @@ impl HipCas {
         let mut steps = 0u64;
         let seed_keys: Vec<u64> = existing.iter().map(|e| e.cas_id.0).collect();
         let seed_ids: Vec<u32> = existing.iter().map(|e| e.id).collect();
+        let pre_ptr = pre.as_ref().map_or(ptr::null(), |p| p.as_ptr());
         let rc = unsafe {
-            sd_cas_identifier_links_ex(self.ctx, keys.as_ptr(), state.as_ptr(), n, chunk,
-                                       seed_keys.as_ptr(), seed_ids.as_ptr(), existing.len(),
-                                       pre.as_ref().map_or(ptr::null(), |p| p.as_ptr()),
-                                       step.as_mut_ptr(), object.as_mut_ptr(), action.as_mut_ptr(),
-                                       counts.as_mut_ptr(), max_steps, &mut steps)
+            match index {
+                Some(h) => sd_cas_identifier_links_indexed(self.ctx, keys.as_ptr(), state.as_ptr(), n, chunk, h,
+                                                           pre_ptr, step.as_mut_ptr(), object.as_mut_ptr(),
+                                                           action.as_mut_ptr(), counts.as_mut_ptr(), max_steps,
+                                                           &mut steps),
+                None => sd_cas_identifier_links_ex(self.ctx, keys.as_ptr(), state.as_ptr(), n, chunk,
+                                                   seed_keys.as_ptr(), seed_ids.as_ptr(), existing.len(),
+                                                   pre_ptr, step.as_mut_ptr(), object.as_mut_ptr(),
+                                                   action.as_mut_ptr(), counts.as_mut_ptr(), max_steps,
+                                                   &mut steps),
+            }
         };
         if rc != 0 {
             return Err(self.err(rc));
@@ -570,6 +635,65 @@ impl HipCas {
             }
         }
         Ok(out)
+    }
+
+    /// A library-resident Object index of this context (sd_cas_index_create): the library's
+    /// (cas_id -> smallest Object id) relation in HBM, filled as Objects are created and read by
+    /// `identifier_links_indexed` and `index_lookup`.  `expected` sizes the table up front
+    /// (0: the minimum; it grows by itself).  At most `SD_CAS_INDEX_MAX` per context.
+    pub fn object_index(&mut self, expected: u64) -> io::Result<ObjectIndex> {
+        let mut handle = 0u32;
+        let rc = unsafe { sd_cas_index_create(self.ctx, expected, &mut handle) };
+        if rc != 0 {
+            return Err(self.err(rc));
+        }
+        Ok(ObjectIndex { handle })
+    }
+
+    /// index[cas_id] = min(what it held, every id given for it here); ids < 2^31, else the
+    /// whole batch is refused and nothing is inserted.
+    pub fn index_insert(&mut self, index: &ObjectIndex, objects: &[ExistingObject]) -> io::Result<()> {
+        let keys: Vec<u64> = objects.iter().map(|e| e.cas_id.0).collect();
+        let ids: Vec<u32> = objects.iter().map(|e| e.id).collect();
+        let rc = unsafe { sd_cas_index_insert(self.ctx, index.handle, keys.as_ptr(), ids.as_ptr(), keys.len()) };
+        if rc != 0 { Err(self.err(rc)) } else { Ok(()) }
+    }
+
+    /// The watcher's `find_first` by cas_id (location/manager/watcher/utils.rs:249-257) and a
+    /// step's `find_many` (file_identifier/mod.rs:181-188): the smallest Object id per cas_id.
+    pub fn index_lookup(&mut self, index: &ObjectIndex, cas_ids: &[CasId]) -> io::Result<Vec<Option<u32>>> {
+        let keys: Vec<u64> = cas_ids.iter().map(|k| k.0).collect();
+        let mut ids = vec![SD_CAS_NO_OBJECT; keys.len()];
+        let rc = unsafe { sd_cas_index_lookup(self.ctx, index.handle, keys.as_ptr(), keys.len(), ids.as_mut_ptr()) };
+        if rc != 0 {
+            return Err(self.err(rc));
+        }
+        Ok(ids.into_iter().map(|v| (v != SD_CAS_NO_OBJECT).then_some(v)).collect())
+    }
+
+    /// Remove cas_ids whatever Object they hold.  When a file_path is deleted or re-identified,
+    /// erase its cas_id and `index_insert` the pairs that remain for it in the DB: the index
+    /// keeps only the minimum per cas_id and cannot tell which ids are left.
+    pub fn index_erase(&mut self, index: &ObjectIndex, cas_ids: &[CasId]) -> io::Result<()> {
+        let keys: Vec<u64> = cas_ids.iter().map(|k| k.0).collect();
+        let rc = unsafe { sd_cas_index_erase(self.ctx, index.handle, keys.as_ptr(), keys.len()) };
+        if rc != 0 { Err(self.err(rc)) } else { Ok(()) }
+    }
+
+    /// The number of cas_ids the index holds.
+    pub fn index_len(&mut self, index: &ObjectIndex) -> io::Result<u64> {
+        let mut st = [0u64; 8];
+        let rc = unsafe { sd_cas_index_stats(self.ctx, index.handle, st.as_mut_ptr()) };
+        if rc != 0 {
+            return Err(self.err(rc));
+        }
+        Ok(st[SD_CAS_INDEX_STAT_ENTRIES])
+    }
+
+    /// Destroy an index before its context goes (which destroys the rest).
+    pub fn index_destroy(&mut self, index: ObjectIndex) -> io::Result<()> {
+        let rc = unsafe { sd_cas_index_destroy(self.ctx, index.handle) };
+        if rc != 0 { Err(self.err(rc)) } else { Ok(()) }
     }
 
     /// `total_object_count` / `total_unique_bytes` of the `statistics` row (statistics.rs:

@@ -76,6 +76,21 @@ SIGNATURES = [
      [_vp, _vp, _vp, _sz, _u32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("sd_cas_identifier_links_ex", _i,
      [_vp, _vp, _vp, _sz, _u32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    ("sd_cas_index_create", _i, [_vp, _u64, ctypes.POINTER(_u32)]),
+    ("sd_cas_index_destroy", _i, [_vp, _u32]),
+    ("sd_cas_index_clear", _i, [_vp, _u32, _vp]),
+    ("sd_cas_index_insert_dev", _i, [_vp, _u32, _vp, _vp, _sz, _vp]),
+    ("sd_cas_index_insert", _i, [_vp, _u32, _vp, _vp, _sz]),
+    ("sd_cas_index_lookup_dev", _i, [_vp, _u32, _vp, _sz, _vp, _vp]),
+    ("sd_cas_index_lookup", _i, [_vp, _u32, _vp, _sz, _vp]),
+    ("sd_cas_index_erase_dev", _i, [_vp, _u32, _vp, _sz, _vp]),
+    ("sd_cas_index_erase", _i, [_vp, _u32, _vp, _sz]),
+    ("sd_cas_index_export_dev", _i, [_vp, _u32, _vp, _vp, _sz, _vp, _vp]),
+    ("sd_cas_index_stats", _i, [_vp, _u32, _vp]),
+    ("sd_cas_identifier_links_indexed_dev", _i,
+     [_vp, _vp, _vp, _sz, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("sd_cas_identifier_links_indexed", _i,
+     [_vp, _vp, _vp, _sz, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("sd_cas_object_stats_dev", _i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("sd_cas_top_duplicates_dev", _i, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     ("sd_cas_duplicate_report", _i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),

@@ -529,7 +529,8 @@ class CasEngine:
         return int(c.value), int(ln.value)
 
     def identifier_links(self, keys, state=None, chunk: int = CHUNK_SIZE,
-                         stream: Optional[int] = None, existing=None, pre_objects=None, out=None):
+                         stream: Optional[int] = None, existing=None, pre_objects=None, out=None,
+                         index: Optional["ObjectIndex"] = None):
         """Object-link emission of one file-identifier job over the rows (ascending
         file_path.id) — sd_cas_identifier_links_ex_dev: returns (step, object, action)
         device tensors (int32, int32, uint8) and the per-step (created, linked) counts as an
@@ -541,8 +542,13 @@ class CasEngine:
         Object its file_path already holds (object_id set, cas_id NULL:
         file_identifier_job.rs:258-261) or -1 (= SD_CAS_NO_OBJECT) — see
         sd_cas_identifier_links_ex_dev.  Ids must be < 2^31 (checked by the library).
+        index: an ObjectIndex of this engine in place of `existing` (not both): the library's
+        Objects are read from it — sd_cas_identifier_links_indexed_dev, the same decisions as
+        existing = index.export() at a cost independent of the library's size.
         out: None or the caller's (step, object, action) tensors to write into."""
         import torch
+        if index is not None and existing is not None:
+            raise ValueError("identifier_links: existing= and index= exclude each other")
         n = int(keys.numel())
         _check_dev(keys, (torch.int64, torch.uint64), n, "keys")
         if state is not None:
@@ -567,6 +573,14 @@ class CasEngine:
             _check_dev(so, (torch.int32, torch.uint32), ns, "existing Object ids")
         if pre_objects is not None:
             _check_dev(pre_objects, (torch.int32, torch.uint32), n, "pre_objects")
+        if index is not None:
+            self._check(self.L.sd_cas_identifier_links_indexed_dev(
+                self.h, _ptr(keys), _ptr(state) if state is not None else None, n, int(chunk),
+                index._handle(self), _ptr(pre_objects) if pre_objects is not None else None,
+                _ptr(step), _ptr(obj), _ptr(act), _np_ptr(counts), ms, ctypes.byref(steps),
+                _stream(stream)), "identifier_links")
+            k = int(steps.value)
+            return step, obj, act, counts[:2 * k].reshape(k, 2).astype(np.int64)
         self._check(self.L.sd_cas_identifier_links_ex_dev(
             self.h, _ptr(keys), _ptr(state) if state is not None else None, n, int(chunk),
             _ptr(sk) if ns else None, _ptr(so) if ns else None, ns,
@@ -577,11 +591,15 @@ class CasEngine:
         return step, obj, act, counts[:2 * k].reshape(k, 2).astype(np.int64)
 
     def identifier_links_host(self, keys: np.ndarray, state: Optional[np.ndarray] = None,
-                              chunk: int = CHUNK_SIZE, existing=None, pre_objects=None):
+                              chunk: int = CHUNK_SIZE, existing=None, pre_objects=None,
+                              index: Optional["ObjectIndex"] = None):
         """sd_cas_identifier_links_ex (host arrays): (step u32, object u32, action u8,
         counts int64 [steps, 2]) — the DB layer's view of the same emission.  existing: None
         or (seed_keys, seed_objects) numpy arrays; pre_objects: None or per-row Object ids
-        (NO_OBJECT / -1 = none) — see identifier_links."""
+        (NO_OBJECT / -1 = none); index: an ObjectIndex in place of `existing` (not both,
+        sd_cas_identifier_links_indexed) — see identifier_links."""
+        if index is not None and existing is not None:
+            raise ValueError("identifier_links_host: existing= and index= exclude each other")
         n = len(keys)
         k = np.ascontiguousarray(keys, dtype=np.uint64)
         st = None if state is None else np.ascontiguousarray(state, dtype=np.uint8)
@@ -604,6 +622,14 @@ class CasEngine:
             po = _object_ids(pre_objects, "pre_objects", none_ok=True)
             if po.shape != (n,):
                 raise ValueError(f"pre_objects has shape {po.shape}, expected ({n},)")
+        if index is not None:
+            self._check(self.L.sd_cas_identifier_links_indexed(
+                self.h, _np_ptr(k), _np_ptr(st) if st is not None else None, n, int(chunk),
+                index._handle(self), _np_ptr(po) if po is not None else None,
+                _np_ptr(step), _np_ptr(obj), _np_ptr(act), _np_ptr(counts), ms, ctypes.byref(steps)),
+                "identifier_links")
+            s = int(steps.value)
+            return step, obj, act, counts[:2 * s].reshape(s, 2).astype(np.int64)
         self._check(self.L.sd_cas_identifier_links_ex(
             self.h, _np_ptr(k), _np_ptr(st) if st is not None else None, n, int(chunk),
             _np_ptr(sk) if ns else None, _np_ptr(so) if ns else None, ns,
@@ -612,6 +638,12 @@ class CasEngine:
             "identifier_links")
         s = int(steps.value)
         return step, obj, act, counts[:2 * s].reshape(s, 2).astype(np.int64)
+
+    def object_index(self, expected: int = 0) -> "ObjectIndex":
+        """A library-resident Object index of this engine (sd_cas_index_create): the library's
+        (cas key -> smallest Object id) relation kept in HBM between calls.  expected: the
+        entries to size the table for (0 = the minimum; it grows by itself)."""
+        return ObjectIndex(self, expected)
 
     def object_stats(self, rep, sizes, copies, totals=None, stream: Optional[int] = None,
                      want_totals: bool = True) -> Optional[dict]:
@@ -1020,6 +1052,138 @@ class CasEngine:
 _DEFAULT: dict[int, CasEngine] = {}
 
 
+INDEX_MAX = 64  # SD_CAS_INDEX_MAX
+INDEX_STAT_NAMES = ("entries", "slots", "tombstones", "rehashes", "last_max_probe")  # SD_CAS_INDEX_STAT_*
+
+
+class ObjectIndex:
+    """sd_cas_index_*: the (cas key -> smallest Object id) relation of a library, resident in HBM
+    and owned by its CasEngine — the reference's SQLite index on cas_id (find_many by cas_id,
+    file_identifier/mod.rs:181-188; the watcher's find_first, watcher/utils.rs:249-257).
+
+    Keys and ids are device tensors (int64/uint64 keys, int32/uint32 ids: the *_dev calls,
+    asynchronous on `stream`) or numpy arrays / sequences (the blocking host forms).  The index
+    keeps the MINIMUM id per key only: when a file_path is deleted or re-identified, erase its
+    key and insert the pairs the DB still holds for that cas_id."""
+
+    def __init__(self, eng: CasEngine, expected: int = 0):
+        h = ctypes.c_uint32(0)
+        eng._check(eng.L.sd_cas_index_create(eng.h, int(expected), ctypes.byref(h)), "index_create")
+        self.eng = eng
+        self.handle: Optional[int] = int(h.value)
+
+    def _handle(self, eng: Optional[CasEngine] = None) -> int:
+        if self.handle is None:
+            raise ValueError("this ObjectIndex is closed")
+        if eng is not None and eng is not self.eng:
+            raise ValueError("an ObjectIndex belongs to the CasEngine that made it")
+        return self.handle
+
+    def close(self) -> None:
+        if self.handle is not None and getattr(self.eng, "h", None):
+            self.eng._check(self.eng.L.sd_cas_index_destroy(self.eng.h, self.handle), "index_destroy")
+        self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @staticmethod
+    def _is_dev(a) -> bool:
+        return hasattr(a, "data_ptr")
+
+    @staticmethod
+    def _host_keys(keys) -> np.ndarray:
+        if isinstance(keys, np.ndarray) and keys.dtype == np.int64:
+            keys = keys.view(np.uint64)
+        return np.ascontiguousarray(keys, dtype=np.uint64)
+
+    def insert(self, keys, objects, stream: Optional[int] = None) -> None:
+        """index[key] = min(what it held, every id given for key here).  An id outside
+        [0, 2^31) refuses the whole batch (CasError EINVAL / ValueError) and inserts nothing."""
+        e, L = self.eng, self.eng.L
+        if self._is_dev(keys):
+            import torch
+            n = int(keys.numel())
+            _check_dev(keys, (torch.int64, torch.uint64), n, "keys")
+            _check_dev(objects, (torch.int32, torch.uint32), n, "objects")
+            e._check(L.sd_cas_index_insert_dev(e.h, self._handle(), _ptr(keys) if n else None,
+                                               _ptr(objects) if n else None, n, _stream(stream)),
+                     "index_insert")
+            return
+        k = self._host_keys(keys)
+        o = _object_ids(objects, "objects", none_ok=False)
+        if len(k) != len(o):
+            raise ValueError("insert: as many Object ids as keys")
+        e._check(L.sd_cas_index_insert(e.h, self._handle(), _np_ptr(k) if len(k) else None,
+                                       _np_ptr(o) if len(k) else None, len(k)), "index_insert")
+
+    def lookup(self, keys, out=None, stream: Optional[int] = None):
+        """The id of every key, NO_OBJECT where the index has none: an int32 device tensor for
+        device keys (`out` to write into one of the caller's), a uint32 numpy array otherwise."""
+        e, L = self.eng, self.eng.L
+        if self._is_dev(keys):
+            import torch
+            n = int(keys.numel())
+            _check_dev(keys, (torch.int64, torch.uint64), n, "keys")
+            if out is None:
+                out = torch.empty(n, dtype=torch.int32, device=keys.device)
+            _check_dev(out, (torch.int32, torch.uint32), n, "out")
+            e._check(L.sd_cas_index_lookup_dev(e.h, self._handle(), _ptr(keys) if n else None, n,
+                                               _ptr(out) if n else None, _stream(stream)), "index_lookup")
+            return out
+        k = self._host_keys(keys)
+        o = np.full(len(k), NO_OBJECT, dtype=np.uint32)
+        e._check(L.sd_cas_index_lookup(e.h, self._handle(), _np_ptr(k) if len(k) else None, len(k),
+                                       _np_ptr(o) if len(k) else None), "index_lookup")
+        return o
+
+    def erase(self, keys, stream: Optional[int] = None) -> None:
+        """Remove the keys whatever id they hold (absent and repeated keys are fine)."""
+        e, L = self.eng, self.eng.L
+        if self._is_dev(keys):
+            import torch
+            n = int(keys.numel())
+            _check_dev(keys, (torch.int64, torch.uint64), n, "keys")
+            e._check(L.sd_cas_index_erase_dev(e.h, self._handle(), _ptr(keys) if n else None, n,
+                                              _stream(stream)), "index_erase")
+            return
+        k = self._host_keys(keys)
+        e._check(L.sd_cas_index_erase(e.h, self._handle(), _np_ptr(k) if len(k) else None, len(k)),
+                 "index_erase")
+
+    def clear(self, stream: Optional[int] = None) -> None:
+        e = self.eng
+        e._check(e.L.sd_cas_index_clear(e.h, self._handle(), _stream(stream)), "index_clear")
+
+    def stats(self) -> dict:
+        """SD_CAS_INDEX_STAT_* keyed by INDEX_STAT_NAMES (blocks)."""
+        e = self.eng
+        st = np.zeros(8, dtype=np.uint64)
+        e._check(e.L.sd_cas_index_stats(e.h, self._handle(), _np_ptr(st)), "index_stats")
+        return {name: int(st[i]) for i, name in enumerate(INDEX_STAT_NAMES)}
+
+    def __len__(self) -> int:
+        return self.stats()["entries"]
+
+    def export(self, device=None, stream: Optional[int] = None):
+        """The live pairs in unspecified order as device tensors (keys int64, ids int32) — what
+        `existing=` of identifier_links takes (blocks)."""
+        import torch
+        e = self.eng
+        dev = device if device is not None else f"cuda:{e.device}"
+        n = len(self)
+        keys = torch.empty(n, dtype=torch.int64, device=dev)
+        ids = torch.empty(n, dtype=torch.int32, device=dev)
+        got = ctypes.c_uint64(0)
+        e._check(e.L.sd_cas_index_export_dev(e.h, self._handle(), _ptr(keys) if n else None,
+                                             _ptr(ids) if n else None, n, ctypes.byref(got),
+                                             _stream(stream)), "index_export")
+        return keys[:int(got.value)], ids[:int(got.value)]
+
+
 def engine(device: int = 0) -> CasEngine:
     if device not in _DEFAULT:
         _DEFAULT[device] = CasEngine(device)
@@ -1090,7 +1254,7 @@ class StepResult:
 
 def identifier_job_step(paths: Sequence[str], chunk: int = CHUNK_SIZE,
                         eng: Optional[CasEngine] = None, existing=None,
-                        pre_objects=None) -> StepResult:
+                        pre_objects=None, index: Optional[ObjectIndex] = None) -> StepResult:
     """Run the file identifier over ``paths`` (ascending file_path.id order: the rows the
     job's orphan query returns — object/cas NULL and indexed size != 0, orphan_path_filters,
     file_identifier_job.rs:251-277) as file_identifier_job.rs:180-236 / mod.rs:98-350 would:
@@ -1104,8 +1268,12 @@ def identifier_job_step(paths: Sequence[str], chunk: int = CHUNK_SIZE,
     watcher gave an Object while it was empty, then written: object_id set, cas_id NULL,
     watcher/utils.rs:236-293,473-490) or None / -1 — such rows and the rows of their step
     with the same cas_id link to the smallest Object carrying it (sd_cas_identifier_links_ex).
+    index: an ObjectIndex of `eng` in place of `existing` (not both): the library's Objects are
+    read from it; the Objects the DB then creates are the caller's to insert.
     Returns the per-file decisions, the per-step batches and the summed (created, linked)."""
-    eng = eng or engine()
+    if index is not None and existing is not None:
+        raise ValueError("identifier_job_step: existing= and index= exclude each other")
+    eng = eng or (index.eng if index is not None else engine())
     res = StepResult()
     n = len(paths)
     if n == 0:
@@ -1127,7 +1295,7 @@ def identifier_job_step(paths: Sequence[str], chunk: int = CHUNK_SIZE,
         ek = np.array([cas_id_to_key(x) if isinstance(x, str) else int(x) for x in ek], dtype=np.uint64)
         seed = (ek, np.asarray(eo, dtype=np.uint32))
     step, obj, act, counts = eng.identifier_links_host(all_keys, state, chunk, existing=seed,
-                                                       pre_objects=pre_objects)
+                                                       pre_objects=pre_objects, index=index)
     res.steps = [StepBatch(k, total_created=int(c), total_linked=int(ln))
                  for k, (c, ln) in enumerate(counts)]
     for i in range(n):

@@ -1,6 +1,6 @@
 // ctx_internal.h — the sd_cas_ctx object and the host helpers shared by the C-ABI
-// translation units (sd_hip_cas.cpp, group_host.cpp, links_host.cpp, reports_host.cpp,
-// host_paths.cpp, validator_host.cpp, sd_multi.cpp).  Not part of the public ABI.
+// translation units (sd_hip_cas.cpp, group_host.cpp, links_host.cpp, object_index_host.cpp,
+// reports_host.cpp, host_paths.cpp, validator_host.cpp, sd_multi.cpp).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dirent.h>
@@ -191,6 +191,8 @@ struct RegionChain {
   hipEvent_t done[2] = {nullptr, nullptr}, hashed[2] = {nullptr, nullptr};
 };
 
+struct sd_object_index;  // a library-resident Object index (object_index_host.cpp)
+
 struct sd_cas_ctx {
   int device = 0;
   hipStream_t stream = nullptr;  // compute
@@ -225,6 +227,11 @@ struct sd_cas_ctx {
   // them), so the chain has no zeroing launch; ordered across streams like ws
   uint32_t* gtotals = nullptr;
   RegionChain regions;  // the fused hash + group chain's two region sets
+  // the context's Object indexes by handle (sd_cas_index_create), destroyed with it
+  sd_object_index* index[SD_CAS_INDEX_MAX] = {};
+  // SD_CAS_INDEX_LOAD_PERCENT=10..90 (measurement knob, read at creation): the indexes' maximum
+  // load in place of INDEX_LOAD_PERCENT (sd_object_index_plan.h); 0 = the built-in value
+  uint32_t index_load_percent = 0;
   // ws and d_scalar are shared by every device call of the context, whatever stream the
   // caller passes: the last enqueued use is recorded here and a use on another stream
   // waits for it first (WsLease)
@@ -463,6 +470,7 @@ struct ExactReportWs {
   uint64_t* ckeys; uint8_t* cdigests; uint32_t *crows, *prior, *crep; uint64_t* sizes; uint8_t* state;
   uint32_t *rep, *copies, *top_heads; uint64_t* top_waste; size_t bytes;
 };
+struct IndexIoWs { uint64_t* keys; uint32_t* objects; size_t bytes; };
 struct StagedLayout { size_t packed, sizes, poffs, plens, keys, h2d_bytes, bytes; };
 struct MultiBufs {
   uint64_t* skeys; uint32_t* sidx; uint64_t* gidx; uint64_t* splits; uint64_t* back;
@@ -479,6 +487,7 @@ TopWs sd_top_layout(void* ws, uint64_t n, uint64_t m);
 DupReportWs sd_dup_report_layout(void* base, size_t n, bool state, size_t k);
 ExactWs sd_exact_layout(void* base, size_t n);
 ExactReportWs sd_exact_report_layout(void* base, size_t n, size_t m, size_t k);
+IndexIoWs sd_index_io_layout(void* base, size_t n);
 }
 
 inline int sd_ensure_pinned(sd_cas_ctx* c, size_t bytes) {
@@ -497,6 +506,14 @@ inline int sd_ensure_pinned(sd_cas_ctx* c, size_t bytes) {
   c->pinned_bytes = want;
   return SD_CAS_OK;
 }
+
+// The Object indexes of a context (object_index_host.cpp).  free_all: at context destruction (the
+// device is idle).  lookup_min: d_inout[i] = min(d_inout[i], index[d_keys[i]]) on s, ordered with
+// the other calls on that index — the link emission's read of it; SD_CAS_EINVAL on a bad handle.
+void sd_index_free_all(sd_cas_ctx* c);
+int sd_index_lookup_min(sd_cas_ctx* c, uint32_t index, const uint64_t* d_keys, uint64_t n,
+                        uint32_t* d_inout, hipStream_t s);
+bool sd_index_alive(const sd_cas_ctx* c, uint32_t index);
 
 // short names for the shared helpers, as the C-ABI translation units write them
 #define fail sd_fail

@@ -48,21 +48,28 @@ LinkIoWs sd_link_io_layout(void* base, size_t n, size_t n_seed, bool pre) {
   L.bytes = w.bytes();  return L;
 }
 
-int sd_cas_identifier_links_ex_dev(sd_cas_ctx* c, const uint64_t* d_keys, const uint8_t* d_state,
-                                   size_t n, uint32_t chunk, const uint64_t* d_seed_keys,
-                                   const uint32_t* d_seed_objects, size_t n_seed,
-                                   const uint32_t* d_pre_objects, uint32_t* d_step,
-                                   uint32_t* d_object, uint8_t* d_action, uint64_t* h_step_counts,
-                                   size_t max_steps, uint64_t* out_steps, void* stream) {
+}  // extern "C"
+
+// The emission behind every device form.  The Objects that exist before the job come either as
+// seed arrays, grouped together with the rows, or (index != NULL, no seeds) from a
+// library-resident Object index: then the rows are grouped alone and every hashed row's minimum is
+// lowered to its key's id in the index, which gives the seeded grouping's result for seeds = the
+// index's pairs (an id is below every ROW_FLAG | row, SD_CAS_NO_OBJECT above).
+static int links_emit(sd_cas_ctx* c, const uint64_t* d_keys, const uint8_t* d_state, size_t n,
+                      uint32_t chunk, const uint64_t* d_seed_keys, const uint32_t* d_seed_objects,
+                      size_t n_seed, const uint32_t* index, const uint32_t* d_pre_objects,
+                      uint32_t* d_step, uint32_t* d_object, uint8_t* d_action, uint64_t* h_step_counts,
+                      size_t max_steps, uint64_t* out_steps, void* stream) {
   if (!c) return SD_CAS_EINVAL;
   const size_t steps_total = sd_cas_identifier_max_steps(n, chunk);
   if (chunk == 0 || n >= (1ull << 32) || !out_steps || max_steps < steps_total ||
       (n && (!d_keys || !d_step || !d_object || !d_action || !h_step_counts)) ||
       (n_seed && (!d_seed_keys || !d_seed_objects)))
     return fail(c, SD_CAS_EINVAL, "identifier_links: bad arguments");
+  if (index && !sd_index_alive(c, *index)) return fail(c, SD_CAS_EINVAL, "identifier_links: no index %u", *index);
   // a seeded grouping tags rows with LINKS_ROW_FLAG: rows and Object ids below 2^31 (rows
-  // that already own an Object run the seeded grouping too)
-  const bool seeded = n_seed > 0 || d_pre_objects;
+  // that already own an Object run the seeded grouping too, and so do rows read against an index)
+  const bool seeded = n_seed > 0 || d_pre_objects || index;
   if (seeded && (n >= LINKS_ROW_FLAG || n_seed >= LINKS_ROW_FLAG || n + n_seed >= (1ull << 32)))
     return fail(c, SD_CAS_EINVAL, "identifier_links: %zu rows + %zu existing Objects exceed 2^31",
                 n, n_seed);
@@ -100,6 +107,7 @@ int sd_cas_identifier_links_ex_dev(sd_cas_ctx* c, const uint64_t* d_keys, const 
     }
     if (cnt[0]) {
       if ((rc = sd_cas_group_min_dev(c, L.hkeys, L.hrows, cnt[0] + n_seed, L.minrow, nullptr, s))) return rc;
+      if (index && (rc = sd_index_lookup_min(c, *index, L.hkeys, cnt[0], L.minrow, s))) return rc;
       HIP_TRY(c, links_scatter(L.minrow, L.hrows, cnt[0], L.rep, seeded ? LINKS_ROW_FLAG : 0u, s));
     }
     HIP_TRY(c, hipStreamSynchronize(s));
@@ -173,6 +181,27 @@ int sd_cas_identifier_links_ex_dev(sd_cas_ctx* c, const uint64_t* d_keys, const 
   return SD_CAS_OK;
 }
 
+extern "C" {
+
+int sd_cas_identifier_links_ex_dev(sd_cas_ctx* c, const uint64_t* d_keys, const uint8_t* d_state,
+                                   size_t n, uint32_t chunk, const uint64_t* d_seed_keys,
+                                   const uint32_t* d_seed_objects, size_t n_seed,
+                                   const uint32_t* d_pre_objects, uint32_t* d_step,
+                                   uint32_t* d_object, uint8_t* d_action, uint64_t* h_step_counts,
+                                   size_t max_steps, uint64_t* out_steps, void* stream) {
+  return links_emit(c, d_keys, d_state, n, chunk, d_seed_keys, d_seed_objects, n_seed, nullptr,
+                    d_pre_objects, d_step, d_object, d_action, h_step_counts, max_steps, out_steps, stream);
+}
+
+int sd_cas_identifier_links_indexed_dev(sd_cas_ctx* c, const uint64_t* d_keys, const uint8_t* d_state,
+                                        size_t n, uint32_t chunk, uint32_t index,
+                                        const uint32_t* d_pre_objects, uint32_t* d_step,
+                                        uint32_t* d_object, uint8_t* d_action, uint64_t* h_step_counts,
+                                        size_t max_steps, uint64_t* out_steps, void* stream) {
+  return links_emit(c, d_keys, d_state, n, chunk, nullptr, nullptr, 0, &index, d_pre_objects, d_step,
+                    d_object, d_action, h_step_counts, max_steps, out_steps, stream);
+}
+
 int sd_cas_identifier_links_seeded_dev(sd_cas_ctx* c, const uint64_t* d_keys, const uint8_t* d_state,
                                        size_t n, uint32_t chunk, const uint64_t* d_seed_keys,
                                        const uint32_t* d_seed_objects, size_t n_seed, uint32_t* d_step,
@@ -192,12 +221,14 @@ int sd_cas_identifier_links_dev(sd_cas_ctx* c, const uint64_t* d_keys, const uin
                                             stream);
 }
 
-int sd_cas_identifier_links_ex(sd_cas_ctx* c, const uint64_t* h_keys, const uint8_t* h_state,
-                               size_t n, uint32_t chunk, const uint64_t* h_seed_keys,
-                               const uint32_t* h_seed_objects, size_t n_seed,
-                               const uint32_t* h_pre_objects, uint32_t* h_step, uint32_t* h_object,
-                               uint8_t* h_action, uint64_t* h_step_counts, size_t max_steps,
-                               uint64_t* out_steps) {
+}  // extern "C"
+
+// the host forms: the rows (and seeds) staged in c->io, links_emit, the decisions copied back
+static int links_emit_host(sd_cas_ctx* c, const uint64_t* h_keys, const uint8_t* h_state, size_t n,
+                           uint32_t chunk, const uint64_t* h_seed_keys, const uint32_t* h_seed_objects,
+                           size_t n_seed, const uint32_t* index, const uint32_t* h_pre_objects,
+                           uint32_t* h_step, uint32_t* h_object, uint8_t* h_action,
+                           uint64_t* h_step_counts, size_t max_steps, uint64_t* out_steps) {
   if (!c) return SD_CAS_EINVAL;
   if ((n && (!h_keys || !h_step || !h_object || !h_action)) ||
       (n_seed && (!h_seed_keys || !h_seed_objects)))
@@ -211,8 +242,8 @@ int sd_cas_identifier_links_ex(sd_cas_ctx* c, const uint64_t* h_keys, const uint
         return fail(c, SD_CAS_EINVAL, "identifier_links: row %zu's Object id %u >= 2^31", i,
                     h_pre_objects[i]);
   if (n == 0 || n >= (1ull << 32))
-    return sd_cas_identifier_links_dev(c, nullptr, nullptr, n, chunk, nullptr, nullptr, nullptr,
-                                       h_step_counts, max_steps, out_steps, c->stream);
+    return links_emit(c, nullptr, nullptr, n, chunk, nullptr, nullptr, 0, index, nullptr, nullptr, nullptr,
+                      nullptr, h_step_counts, max_steps, out_steps, c->stream);
   HIP_TRY(c, hipSetDevice(c->device));
   int rc = ensure(c, c->io, sd_link_io_layout(nullptr, n, n_seed, h_pre_objects != nullptr).bytes);
   if (rc) return rc;
@@ -226,15 +257,35 @@ int sd_cas_identifier_links_ex(sd_cas_ctx* c, const uint64_t* h_keys, const uint
     HIP_TRY(c, hipMemcpyAsync(L.seed_objects, h_seed_objects, n_seed * 4, hipMemcpyHostToDevice, s));
   }
   if (L.pre) HIP_TRY(c, hipMemcpyAsync(L.pre, h_pre_objects, n * 4, hipMemcpyHostToDevice, s));
-  rc = sd_cas_identifier_links_ex_dev(c, L.keys, d_state, n, chunk, L.seed_keys, L.seed_objects,
-                                      n_seed, L.pre, L.step, L.object, L.action, h_step_counts,
-                                      max_steps, out_steps, s);
+  rc = links_emit(c, L.keys, d_state, n, chunk, L.seed_keys, L.seed_objects, n_seed, index, L.pre, L.step,
+                  L.object, L.action, h_step_counts, max_steps, out_steps, s);
   if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(h_step, L.step, n * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipMemcpyAsync(h_object, L.object, n * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipMemcpyAsync(h_action, L.action, n, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   return SD_CAS_OK;
+}
+
+extern "C" {
+
+int sd_cas_identifier_links_ex(sd_cas_ctx* c, const uint64_t* h_keys, const uint8_t* h_state,
+                               size_t n, uint32_t chunk, const uint64_t* h_seed_keys,
+                               const uint32_t* h_seed_objects, size_t n_seed,
+                               const uint32_t* h_pre_objects, uint32_t* h_step, uint32_t* h_object,
+                               uint8_t* h_action, uint64_t* h_step_counts, size_t max_steps,
+                               uint64_t* out_steps) {
+  return links_emit_host(c, h_keys, h_state, n, chunk, h_seed_keys, h_seed_objects, n_seed, nullptr,
+                         h_pre_objects, h_step, h_object, h_action, h_step_counts, max_steps, out_steps);
+}
+
+int sd_cas_identifier_links_indexed(sd_cas_ctx* c, const uint64_t* h_keys, const uint8_t* h_state,
+                                    size_t n, uint32_t chunk, uint32_t index,
+                                    const uint32_t* h_pre_objects, uint32_t* h_step, uint32_t* h_object,
+                                    uint8_t* h_action, uint64_t* h_step_counts, size_t max_steps,
+                                    uint64_t* out_steps) {
+  return links_emit_host(c, h_keys, h_state, n, chunk, nullptr, nullptr, 0, &index, h_pre_objects, h_step,
+                         h_object, h_action, h_step_counts, max_steps, out_steps);
 }
 
 int sd_cas_identifier_links_seeded(sd_cas_ctx* c, const uint64_t* h_keys, const uint8_t* h_state,

@@ -1,9 +1,10 @@
 // sd_hip_cas.cpp — the core of the C ABI (include/sd_hip_cas.h) over the gfx950 kernels: the
 // debug library's allocation tails, contexts and their setters, the hex helpers, the device-resident
 // cas dispatch (K1 / K1L / K2 by batch size) and the synthetic inputs.  The other entry points:
-// grouping and the fused chain in group_host.cpp, link emission in links_host.cpp, statistics,
-// reports and exact duplicates in reports_host.cpp, host buffers and paths in host_paths.cpp, the
-// validator in validator_host.cpp, several devices in sd_multi.cpp.
+// grouping and the fused chain in group_host.cpp, link emission in links_host.cpp, the Object index
+// in object_index_host.cpp, statistics, reports and exact duplicates in reports_host.cpp, host
+// buffers and paths in host_paths.cpp, the validator in validator_host.cpp, several devices in
+// sd_multi.cpp.
 //
 // Host runtime for the batched drop-in of generate_cas_id (core/src/object/cas.rs:23-62),
 // its batch caller identifier_job_step (core/src/object/file_identifier/mod.rs:98-350)
@@ -36,6 +37,7 @@ uint32_t sd_dbg_violations_inplace();
 uint32_t sd_dbg_violations_object_stats();
 uint32_t sd_dbg_violations_exact_dups();
 uint32_t sd_dbg_violations_content_compare();
+uint32_t sd_dbg_violations_object_index();
 }  // namespace sdcas
 // debug library only (libsd_hip_cas_debug.so, not in the ABI header): invariant violations
 // counted by the device checks of sd_debug.h since the library was loaded
@@ -45,7 +47,7 @@ extern "C" uint64_t sd_cas_debug_violations(void) {
          sd_dbg_violations_dup_verify() + sd_dbg_violations_group() +
          sd_dbg_violations_checksum() + sd_dbg_violations_links() + sd_dbg_violations_inplace() +
          sd_dbg_violations_object_stats() + sd_dbg_violations_exact_dups() +
-         sd_dbg_violations_content_compare() + sd_dbg_tail_check_all();
+         sd_dbg_violations_content_compare() + sd_dbg_violations_object_index() + sd_dbg_tail_check_all();
 }
 
 // The allocation tails of ctx_internal.h: every device buffer of a context is followed by
@@ -270,6 +272,11 @@ int sd_cas_ctx_create(int device, sd_cas_ctx** out) {
       }
       c->dupv.placement = !strcmp(p, "cu") ? DUP_PLACE_CU : !strcmp(p, "static") ? DUP_PLACE_STATIC : DUP_PLACE_AUTO;
     }
+    // measurement knob: the Object indexes' maximum load (tools/bench_object_index.py sweeps it);
+    // results are the same at every value, only table sizes and probe lengths differ
+    const char* l = getenv("SD_CAS_INDEX_LOAD_PERCENT");
+    const long lv = l && *l ? strtol(l, nullptr, 10) : 0;
+    c->index_load_percent = lv >= 10 && lv <= 90 ? (uint32_t)lv : 0u;
   }
   bind_pool_to_gpu_node(c);
   // the pool's readers on private descriptor tables (HostPool::set_private_fds)
@@ -315,6 +322,7 @@ void sd_cas_ctx_destroy(sd_cas_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
+  sd_index_free_all(c);
   for (DevBuf* b : {&c->ws, &c->staging, &c->small, &c->cvbuf, &c->io, &c->inplace, &c->dupv.buf, &c->exact,
                     &c->contents})
     if (b->p) (void)sd_dev_free(b->p);
